@@ -2,13 +2,18 @@
 """bench.py — RTF / audio-seconds-per-second of the chunk path; default = GTCRN at batch = 256 x 1 s chunks (BASELINE.json configs[1]).
 
 `--workload zipenhancer | melband | mossformer` selects the other BASELINE configs (configs[2] / [3] / [4]) at their own batch shapes as the headline;
-the default invocation's line also carries them, briefly timed, in `other_workloads` (so that the driver's clock covers every BASELINE config; `--other`, `--other-steps`).
+with `--full` the gtcrn line also carries them, briefly timed, in `other_workloads` (`--other`, `--other-steps`).
+
+A plain run sets up, warms up, times `--steps` steps, writes the last step's output if `--dump-outputs DIR` is given and prints the line.  `--full` adds
+every leg beside the headline: the host-inclusive loops, per-kernel times and the roofline, the CPU baselines, the STFT operator, the other workloads and
+the bf16-vs-f32 deviation of a bf16 line.
 
 A "step" is one pass of the hot path (int16 PCM in HBM -> STFT -> GTCRN -> mask -> ISTFT/OLA -> int16 PCM in HBM)
 over one batch of 256 synthetic 1 s chunks per GPU (`configs[1]`), through libade's C ABI on device buffers.
 Weights: seeded reference-architecture weights (tests/golden/gtcrn_seed0.adew; the reference ships no checkpoint).
 
     python bench.py --gpus 1 --steps 100 --warmup 10
+    python bench.py --gpus 1 --steps 100 --warmup 10 --full --dump-outputs out/      # every leg, and the last step's output as out/pcm_out.npy
     python bench.py --gpus N ...                      # N > 1 outside a launcher: re-executes itself under torch.distributed.run with N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 8 --workload melband --dtype bf16 --stitch      # BASELINE configs[3] with its RCCL all-gather of the outputs, one command
@@ -73,11 +78,17 @@ FP32_PEAK_TFLOPS = 157.3                           # fp32 dense: f32-MFMA rate =
 BF16_PEAK_TFLOPS = 2500.0                          # dense bf16 MFMA (MI355X_MICROARCH.md)
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 100 for gtcrn, 10 for the other workloads)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default: 10 for gtcrn, 2 for the other workloads)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the host-inclusive and pipelined host loops, per-kernel times and the roofline, the CPU baselines, the "
+                         "STFT operator, the other workloads and the bf16-vs-f32 deviation.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the int16 PCM the last step produced as DIR/pcm_out.npy (float32, rows x samples; rank 0's rows, all ranks' "
+                         "with --stitch); above 64 MB a fixed seeded sample of rows, in order")
     ap.add_argument("--workload", default="gtcrn", choices=["gtcrn", "zipenhancer", "melband", "mossformer", "dfsmn"],
                     help="BASELINE.json config: gtcrn = configs[1] (default), zipenhancer = [2], melband = [3], mossformer = [4]; dfsmn = north_star's fourth network "
                          "(256 x 2 s @ 48 kHz, no BASELINE config of its own)")
@@ -85,23 +96,29 @@ def parse_args():
                     help="f32 = exact fp32 matrix-core products (parity path, default); bf16 = bf16 activations and weights stored in HBM (--workload melband only: "
                          "csrc/ade_gemm16.h).  The deviation from the f32 path is measured and reported")
     ap.add_argument("--batch", type=int, default=0, help="chunks per GPU per step (0 = the workload's BASELINE batch: 256 / 128 / 32 / 64)")
-    ap.add_argument("--host-steps", type=int, default=20, help="steps of the host-inclusive leg (pinned host buffers through ade_process; 0 = skip)")
+    ap.add_argument("--host-steps", type=int, default=20, help="steps of the host-inclusive leg (--full; pinned host buffers through ade_process; 0 = skip)")
     ap.add_argument("--stitch", action="store_true", help="all-gather the int16 outputs (RCCL) inside the timed region")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): every rank runs its own --batch chunks; strong: ONE batch of --batch chunks (default: the workload's BASELINE batch) is dealt over the "
                          "ranks in contiguous blocks of ceil(B / N), the way the file drivers shard a file's slices (distributed.shard_bounds; trailing ranks may be idle)")
-    ap.add_argument("--other-cpu-seconds", type=float, default=60.0, help="budget of the CPU-oracle legs of the `other_workloads` block (0 = skip them)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-oracle baseline leg (0 = skip)")
+    ap.add_argument("--other-cpu-seconds", type=float, default=60.0, help="budget of the CPU-oracle legs of the `other_workloads` block (--full; 0 = skip them)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-oracle baseline leg (--full; 0 = skip)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-deviation", action="store_true", help="skip the bf16-vs-f32 deviation run of a --dtype bf16 line (profiling runs)")
+    ap.add_argument("--no-deviation", action="store_true", help="skip the bf16-vs-f32 deviation run of a --full --dtype bf16 line (profiling runs)")
     ap.add_argument("--geometry", default="auto", choices=["auto", "0", "1", "2"],
                     help="GTCRN fused-path workgroup geometry: 2 = four 256-thread workgroups per CU, each a 16-frame segment of a chunk (default where it fits); "
                          "1 = two 512-thread workgroups per CU (32-frame segments); 0 = one 1024-thread workgroup per chunk (the round-1/2 kernel)")
-    ap.add_argument("--other", default="zipenhancer,melband,mossformer,dfsmn", help="which of the other BASELINE configs the default line times in its `other_workloads` block")
-    ap.add_argument("--other-steps", type=int, default=3, help="timed steps of the `other_workloads` leg of the default line (ZipEnhancer 128 x 1 s, f32; 0 = skip)")
+    ap.add_argument("--other", default="zipenhancer,melband,mossformer,dfsmn", help="which of the other BASELINE configs the --full gtcrn line times in its `other_workloads` block")
+    ap.add_argument("--other-steps", type=int, default=3, help="timed steps of the `other_workloads` leg of the --full gtcrn line (ZipEnhancer 128 x 1 s, f32; 0 = skip)")
     ap.add_argument("--ramp-ms", type=float, default=100.0, help="untimed power-state ramp before the W warm-up steps (0 = none)")
-    ap.add_argument("--no-stft-operator", action="store_true", help="skip the `stft_operator` block (the generic STFT_Process operator's HBM roofline) of the default line")
-    return ap.parse_args()
+    ap.add_argument("--no-stft-operator", action="store_true", help="skip the `stft_operator` block (the generic STFT_Process operator's HBM roofline) of the --full gtcrn line")
+    args = ap.parse_args(argv)
+    # default step counts: GTCRN's steps take 0.4 ms, the other workloads' 0.2 - 1.2 s; an explicit --steps / --warmup always holds
+    if args.steps is None:
+        args.steps = 100 if args.workload == "gtcrn" else 10
+    if args.warmup is None:
+        args.warmup = 10 if args.workload == "gtcrn" else 2
+    return args
 
 
 # The translation units and headers k_gtcrn_chunk and the per-stage kernels are compiled from; the other families' sources do not change those kernels.
@@ -472,6 +489,20 @@ def build_audio_metadata_dfsmn(length: int):
                                 pad_mode="constant", feature_kind="kaldi_fbank_stft")
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, d_out) -> None:
+    """The int16 PCM of the last timed step, as a caller of the path receives it, -> out_dir/pcm_out.npy in float32 (exact for int16).  Above DUMP_LIMIT_BYTES a fixed
+    seeded sample of whole rows is written, in row order, so that two builds of the project can be compared output for output."""
+    pcm = d_out.cpu().numpy().astype(np.float32)                # (rows, samples)
+    if pcm.nbytes > DUMP_LIMIT_BYTES:
+        keep = np.random.default_rng(0).choice(pcm.shape[0], DUMP_LIMIT_BYTES // (4 * pcm.shape[1]), replace=False)
+        pcm = pcm[np.sort(keep)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pcm_out.npy"), pcm)
+
+
 def relaunch_command(n: int, argv, port: int):
     """The launcher line `--gpus N` (N > 1) stands for when bench.py is started bare: one rank per GPU on this node, rendezvous on the loopback address."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1", "--master-port", str(port),
@@ -504,7 +535,7 @@ def main():
             port = so.getsockname()[1]
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
         raise SystemExit(subprocess.call(relaunch_command(args.gpus, sys.argv[1:], port), env=env))
-    SKIP_DEVIATION = args.no_deviation
+    SKIP_DEVIATION = args.no_deviation or not args.full
     DEVIATION_DTYPE = args.dtype
     if args.dtype != "f32" and args.workload not in ("melband", "zipenhancer"):
         raise SystemExit("--dtype bf16 (bf16 stored in HBM) exists for the melband and zipenhancer workloads; the other workloads run f32")
@@ -553,8 +584,6 @@ def main():
         B = hi - lo
         wl = build_workload(args.workload, max(B, 1), rank, local_rank, args.dtype)      # (an idle rank of a strong-scaling run still opens its session)
         sess, x_host, sr = wl["sess"], wl["x"][:B], wl["sr"]
-        if args.steps == 100 and args.warmup == 10:      # the defaults are sized for GTCRN's 0.4 ms steps; these steps take 0.2 - 1.2 s
-            args.steps, args.warmup = 10, 2
         args.ramp_ms = 0.0
     if args.no_graph:
         sess.set_option("graph", "0")
@@ -612,6 +641,8 @@ def main():
 
     if gtcrn and sess.tap("xchg_error", 1)[0] != 0.0:      # a segment hand-off of the fused path timed out inside the timed loop: the steps after it are not a measurement
         raise SystemExit("bench.py: the fused path reported an inter-workgroup time-out (xchg_error) during the timed loop; no number is reported")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered if gathered is not None else d_out)
     out_seconds_per_row = sess.out_len / sr
     audio_s_per_step = (B_total if strong else world * B) * out_seconds_per_row
     ms_per_step = 1e3 * elapsed / max(1, args.steps)
@@ -621,7 +652,7 @@ def main():
     # SURVEY.md section 8 d1): the same batch through the host-buffer entry ade_process on page-locked caller buffers.  Reported beside the
     # device-resident headline, never as `value`.
     host_inclusive = None
-    if rank == 0 and args.host_steps > 0:
+    if rank == 0 and args.full and args.host_steps > 0:
         pin_in = torch.from_numpy(x_host.copy()).pin_memory()
         pin_out = torch.empty((B, sess.row_out), dtype=torch.int16).pin_memory()
         p_in, p_out = pin_in.numpy(), pin_out.numpy()
@@ -661,7 +692,7 @@ def main():
                                    "steady_state_note": f"ade_submit / ade_wait, {depth} submissions in flight on page-locked buffers: wall clock per batch over {ps} back-to-back batches"})
 
     roofline = cpu = kernels = others = stft_op = None
-    if rank == 0 and gtcrn:
+    if rank == 0 and args.full and gtcrn:
         # per-kernel device time, HIP events on the launch stream (ade_profile_last), averaged over a few forwards
         def timed(mode, reps=10):
             sess.profile(mode)
@@ -741,7 +772,7 @@ def main():
                     others[key] = other_workload_line(name, steps, local_rank, stream, args.other_cpu_seconds if dt_ == "f32" else 0.0, dt_)
                 except Exception as ex:   # the headline must not depend on it
                     others[key] = {"error": repr(ex)}
-    elif rank == 0:
+    elif rank == 0 and args.full:
         # A GEMM-shaped family is hundreds of launches per step (fp32 matrix-core GEMMs + row kernels), so the roofline object prices the WHOLE
         # step against the dense fp32 matrix rate: achieved = algorithmic flops of the step / the step's device time.  Per-kernel device times and the
         # MFMA-busy counters of the same command are the committed rocprofv3 summaries under profiles/ (named in `evidence`).
@@ -805,7 +836,7 @@ def main():
             line["stft_operator"] = stft_op
         if not gtcrn and wl.get("target_rtf"):
             line["target_rtf"] = wl["target_rtf"]
-        if not gtcrn and args.dtype != "f32":
+        if not gtcrn and args.dtype != "f32" and args.full:
             line["deviation_from_f32"] = wl.get("deviation")
             roofline["frac_of_f32_peak"] = roofline["frac"]                    # comparability with the f32 line (can exceed 1: bf16 inputs run on a faster pipe)
             roofline["peak"] = BF16_PEAK_TFLOPS

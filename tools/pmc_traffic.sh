@@ -5,8 +5,8 @@
 set -e
 OUT=$1; LABEL=$2; shift; shift; R=$PWD; mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $R/$OUT/fetch -- python $R/bench.py --steps 5 --warmup 2 --cpu-seconds 0 --host-steps 0 --other-steps 0 "$@" > $R/$OUT/fetch.log 2>&1 || tail -3 $R/$OUT/fetch.log
-rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $R/$OUT/write -- python $R/bench.py --steps 5 --warmup 2 --cpu-seconds 0 --host-steps 0 --other-steps 0 "$@" > $R/$OUT/write.log 2>&1 || tail -3 $R/$OUT/write.log
+rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $R/$OUT/fetch -- python $R/bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 --host-steps 0 --other-steps 0 "$@" > $R/$OUT/fetch.log 2>&1 || tail -3 $R/$OUT/fetch.log
+rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $R/$OUT/write -- python $R/bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 --host-steps 0 --other-steps 0 "$@" > $R/$OUT/write.log 2>&1 || tail -3 $R/$OUT/write.log
 cd $R
 python3 - "$OUT" "$LABEL" <<'PY'
 import csv, glob, collections, json, re, sys
@@ -26,7 +26,7 @@ for kind in ("fetch", "write"):
         res[k][kind + "_kib"] = round(sum(v) / len(v), 2)
         res[k]["dispatches"] = len(v)
         print(kind, k, "dispatches", len(v), "avg counter", sum(v) / len(v))
-doc = {"_how": "tools/pmc_traffic.sh on one MI355X: rocprofv3 --kernel-trace --pmc FETCH_SIZE and, in a SEPARATE pass, --pmc WRITE_SIZE, of `python bench.py --steps 5 --warmup 2 "
+doc = {"_how": "tools/pmc_traffic.sh on one MI355X: rocprofv3 --kernel-trace --pmc FETCH_SIZE and, in a SEPARATE pass, --pmc WRITE_SIZE, of `python bench.py --full --steps 5 --warmup 2 "
                "--cpu-seconds 0` (batch 256). Values are per-dispatch averages in the counters' native KiB. Correction per MI355X_MICROARCH.md (HBM section): on gfx950 "
                "FETCH_SIZE reports half of the bytes of wide (16 B/lane) coalesced reads, so bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024; WRITE_SIZE is taken as-is (uncalibrated). "
                "Infinity-Cache hits are counted, so this is fabric-side traffic, an upper bound on HBM traffic.",

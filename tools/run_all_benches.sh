@@ -3,7 +3,7 @@
 OUT=${1:-gpurun_out/all_benches.txt}
 mkdir -p "$(dirname "$OUT")"
 {
-  echo "== bench.py (north star: GTCRN 256 x 1 s)"; python bench.py 2>/dev/null | tail -1
+  echo "== bench.py (north star: GTCRN 256 x 1 s)"; python bench.py --full 2>/dev/null | tail -1
   echo "== tools/bench_host_path.py"; python tools/bench_host_path.py 2>/dev/null | tail -2
   echo "== tools/bench_streaming.py"; python tools/bench_streaming.py 2>/dev/null | tail -6
   echo "== tools/bench_dfsmn.py"; python tools/bench_dfsmn.py 2>/dev/null | tail -4
