@@ -1037,8 +1037,11 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
     }
     const bool fam_dfsmn = e->meta["model_family"] == "dfsmn", fam_melband = e->meta["model_family"] == "mel_band_roformer",
                fam_moss = e->meta["model_family"] == "mossformer2_ss", fam_ulu = e->meta["model_family"] == "ul_unas",
-               fam_hg = e->meta["model_family"] == "h_gtcrn", fam_zip = e->meta["model_family"] == "zipenhancer";
-    if (fam_dfsmn || fam_melband || fam_moss || fam_ulu || fam_hg || fam_zip) {   // DFSMN/Export_DFSMN.py (48 kHz mono) / Mel_Band_Roformer/Stereo/Export_MelBandRoformer.py (44.1 kHz stereo)
+               fam_hg = e->meta["model_family"] == "h_gtcrn", fam_zip = e->meta["model_family"] == "zipenhancer",
+               fam_nkf = e->meta["model_family"] == "nkf_aec";
+    if (fam_nkf && !ade::nkf_aec_create)            // a library linked without csrc/ade_nkf_aec.hip (weak symbol)
+        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'nkf_aec' is not built into this library"));
+    if (fam_dfsmn || fam_melband || fam_moss || fam_ulu || fam_hg || fam_zip || fam_nkf) {   // DFSMN/Export_DFSMN.py (48 kHz mono) / Mel_Band_Roformer/Stereo/Export_MelBandRoformer.py (44.1 kHz stereo)
         const std::string fam = e->meta["model_family"];
         const long rate = fam_dfsmn ? 48000 : fam_melband ? 44100 : 16000;
         bool dyn_d = false, fold_d = false;
@@ -1060,10 +1063,22 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         const bool dyn_sf = dyn_d && (fam_dfsmn || fam_zip || fam_moss);
         // H-GTCRN's (Export_H_GTCRN.py:27, :1075, :1097, :1110): frame counts from the waveform and the ISTFT's dynamic trim -- half a window of tail is kept, L + 256 samples out;
         // its edges interpolate by scale factor in either mode.
+        if (dyn_d && fam_nkf)
+            return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: only static axes exist (Export_NKF_AEC.py:27, 'Only support static axes')"));
+        if (fam_nkf) {      // the one STFT the model was trained with (:31-34); a manifest that names another is not this engine's
+            auto opt = [&](const char* k, const char* want) { auto it = e->meta.find(k); return it == e->meta.end() || it->second.empty() || it->second == want; };
+            if (!opt("nfft", "1024") || !opt("hop_length", "256") || !opt("window_length", "1024") || !opt("window_type", "hann") || !opt("pad_mode", "constant") ||
+                !opt("center_pad", "1"))
+                return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: STFT configuration other than 1024/1024/256 hann constant centre-pad"));
+        }
         if (dyn_d && !fam_sand && !dyn_sf && !fam_hg)
             return bail(fail(e, ADE_ERR_UNSUPPORTED, "dynamic_axes=1 is not implemented for " + fam));
         if (e->meta.count("use_batch_fold") && !e->meta["use_batch_fold"].empty() && !parse_bool(e->meta["use_batch_fold"], &fold_d))
             return bail(fail(e, ADE_ERR_BAD_VALUE, "Metadata key use_batch_fold must be a boolean encoded as 1/0."));
+        // NKF-AEC's folded export is not a batch of independent windows: KGNet_Real._from_grouped (Export_NKF_AEC.py:106-107) reshapes the grouped
+        // (windows, 36, F) activations as if there were one window, which interleaves the real and imaginary channel groups of neighbouring windows.
+        if (fold_d && fam_nkf)
+            return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: use_batch_fold=1 is not implemented (the reference's folded graph mixes the windows' channels)"));
         if (fold_d && fam_dfsmn) {   // a folded window must reconstruct itself: raw overlap-add length 1920 + 960 (T - 1) == W  (Export_DFSMN.py:54)
             long fw = 0;
             if (!e->meta.count("fold_window_length") || !parse_int(e->meta["fold_window_length"], &fw) || fw < 1920 || fw % 960)
@@ -1075,12 +1090,17 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
             return bail(fail(e, ADE_ERR_BAD_VALUE, "manifest: sample rates / input_audio_length must be integers"));
         const bool rates_differ = sri != srm || sro != srm;
         if (srm != rate) return bail(fail(e, ADE_ERR_UNSUPPORTED, fam + " runs at a model rate of " + std::to_string(rate) + " Hz"));
+        // NKF-AEC's static graph sizes its ISTFT from the INPUT-rate length (Export_NKF_AEC.py:33-35), which agrees with the STFT only at 16 kHz in; the output edge
+        // is GTCRN's sandwich (down-sampling before the * 32767, up-sampling after it, :391-406).
+        if (fam_nkf && sri != srm)
+            return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: in_sample_rate must be the model rate, 16000 Hz (the static export sizes its ISTFT from the input-rate length)"));
+        const bool sand_out = fam_sand || fam_nkf;          // families whose output edge is the scale-factor sandwich
         // Resampling edges exist where the reference's STATIC export is self-consistent: MossFormer2 and DFSMN size their frames from the
         // model-rate length (Export_MossFormer2_SS_16K.py:36-37,99-104; Export_DFSMN.py:48,67).  Mel-Band-Roformer (like GTCRN) and UL-UNAS size
         // the static frame count from the INPUT-rate length (Export_MelBandRoformer.py:52), which only agrees with the STFT at equal rates.
         // H-GTCRN's static export is consistent too (frames from MODEL_AUDIO_LENGTH, Export_H_GTCRN.py:45-46); it interpolates by SCALE FACTOR.
         // ZipEnhancer sizes its frames from MODEL_AUDIO_LENGTH too (Export_ZipEnhancer.py:55, 61) and interpolates by size (:826-832, :905-911).
-        if (rates_differ && !fam_moss && !fam_dfsmn && !fam_hg && !fam_zip && !(fam_sand && dyn_d))
+        if (rates_differ && !fam_moss && !fam_dfsmn && !fam_hg && !fam_zip && !fam_nkf && !(fam_sand && dyn_d))
             return bail(fail(e, ADE_ERR_UNSUPPORTED, fam + " runs at " + std::to_string(rate) + " Hz in, model and out (its static export has no consistent resampling path" +
                                                      (fam_sand ? ": export with dynamic_axes=1 for other rates)" : ")")));
         if (dyn_d && fold_d) return bail(fail(e, ADE_ERR_BAD_VALUE, "Batch folding requires a static shape (dynamic_axes=0)."));     // (Export_MelBandRoformer.py:46)
@@ -1150,6 +1170,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                        : fam_ulu     ? ade::ulunas_create(e->tensors, (int)Ld, (int)sub_win, dyn_d ? (int)caller_len : 0, device, &e->sub, derr)
                        : fam_hg      ? ade::hgtcrn_create(e->tensors, (int)Ld, (int)sub_win, dyn_d, device, &e->sub, derr)
                        : fam_zip     ? ade::zipenhancer_create(e->tensors, (int)Ld, (int)sub_win, exact_dft, gemm_bf16, dyn_d, device, &e->sub, derr)
+                       : fam_nkf     ? ade::nkf_aec_create(e->tensors, (int)Ld, device, &e->sub, derr)
                                      : ade::mossformer_create(e->tensors, (int)Ld, (int)sub_win, dyn_d, device, &e->sub, derr);
         if (rc != ADE_OK) return bail(fail(e, (ade_status)rc, derr));
         e->channels = e->sub->channels();
@@ -1163,8 +1184,8 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
             e->rs_model_in = e->sub->in_len();
             e->rs_model_out = e->sub->out_len();
             e->rs_scale_in = 1.0f;
-            e->rs_scale_out = fam_sand ? 0.0f : 1.0f;
-            e->rs_sandwich_out = fam_sand;
+            e->rs_scale_out = sand_out ? 0.0f : 1.0f;
+            e->rs_sandwich_out = sand_out;
             e->rs_pcm_scale = fam_dfsmn ? 32768.0f : fam_hg ? 32767.0f : 1.0f;     // as on the resampling path below
             e->rs_truncate_i32 = !fam_dfsmn && !fam_hg;
         }
@@ -1184,7 +1205,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                 e->rs_scale_in = (float)((double)sri / (double)srm);
                 e->rs_scale_out = (float)((double)srm / (double)sro);
                 e->sub->float_src_len = (int)caller_len;
-            } else if (fam_sand) {   // scale_factor on both edges; down-sampling precedes the * 32767 of an int16 output, up-sampling follows it (Export_MelBandRoformer.py:660-680,
+            } else if (sand_out) {   // scale_factor on both edges; down-sampling precedes the * 32767 of an int16 output, up-sampling follows it (Export_MelBandRoformer.py:660-680,
                 //                                                                                                                     Export_UL_UNAS.py:890-905)
                 const double f_in = fam_ulu ? 1.0 / ((double)sri / 16000.0) : (double)srm / (double)sri, f_out = fam_ulu ? (double)sro / 16000.0 : (double)sro / (double)srm;
                 out_caller = sro == srm ? (long)e->rs_model_out : (long)floor((double)e->rs_model_out * f_out);
@@ -1213,7 +1234,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         return ADE_OK;
     }
     if (e->meta["model_family"] != "gtcrn")
-        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family '" + e->meta["model_family"] + "' is not implemented (gtcrn, h_gtcrn, dfsmn, mel_band_roformer, mossformer2_ss, ul_unas, zipenhancer)"));
+        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family '" + e->meta["model_family"] + "' is not implemented (gtcrn, h_gtcrn, dfsmn, mel_band_roformer, mossformer2_ss, ul_unas, zipenhancer, nkf_aec)"));
     bool dyn = false;
     if (!parse_bool(e->meta["dynamic_axes"], &dyn))
         return bail(fail(e, ADE_ERR_BAD_VALUE, "Metadata key dynamic_axes must be a boolean encoded as 1/0, got '" + e->meta["dynamic_axes"] + "'."));

@@ -285,5 +285,8 @@ int hgtcrn_create(const std::map<std::string, Tensor>& tensors, int window_len, 
 // model_family "zipenhancer" (ZipEnhancer/Export_ZipEnhancer.py:357-927), csrc/ade_zipenhancer.hip
 int zipenhancer_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, bool exact_dft, bool bf16 /* ade_gemm_dtype = bf16: csrc/ade_zip16.h */, bool dynamic /* DYNAMIC_AXES export: divide by the overlap-add denominator */, int device, SubEngine** out, std::string& err);
 int melband_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, bool exact_dft, bool bf16, bool dynamic, int device, SubEngine** out, std::string& err);
+// model_family "nkf_aec" (NKF_AEC/Export_NKF_AEC.py:150-411), csrc/ade_nkf_aec.hip.  Weak: a library linked without that source (the host simulator's fixed
+// source list) resolves it to null, and the engine answers ADE_ERR_UNSUPPORTED for the family.
+int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int device, SubEngine** out, std::string& err) __attribute__((weak));
 
 }  // namespace ade

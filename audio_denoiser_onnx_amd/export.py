@@ -11,6 +11,7 @@ matrices (``ERB.prepare_for_export_`` :109-114), and write the tensors under the
     python -m audio_denoiser_onnx_amd.export --family mossformer2_ss <checkpoint> <out_dir> [--length 24000] [--fold] [--dynamic [--in-rate 8000] [--out-rate 48000]]
     python -m audio_denoiser_onnx_amd.export --family ul_unas <model_trained_on_dns3.tar> <out_dir> [--length 16000]
     python -m audio_denoiser_onnx_amd.export --family zipenhancer <pytorch_model.bin> <out_dir> [--length 32000] [--fold]
+    python -m audio_denoiser_onnx_amd.export --family nkf_aec <nkf_epoch70.pt> <out_dir> [--length 32000] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
 
 The other two families fold their checkpoints the way their export constructors do (``melband.fuse_checkpoint`` =
 Export_MelBandRoformer.py:455-538; ``mossformer.fuse_checkpoint`` = Export_MossFormer2_SS_16K.py:130-395); both folds are
@@ -184,6 +185,20 @@ def export_zipenhancer(checkpoint, out_dir, input_audio_length: int = 32000, use
     return model_path
 
 
+def export_nkf_aec(checkpoint, out_dir, input_audio_length: int = 32000, name: str = "NKF_AEC", out_sample_rate: int = 16000,
+                   input_audio_dtype: str = "INT16", output_audio_dtype: str = "INT16") -> Path:
+    """NKF-AEC checkpoint (``nkf_epoch70.pt``: the plain state dict of the original model, key names of ``load_nkf_weights``, Export_NKF_AEC.py:414-455)
+    -> ``<name>.adew`` + manifest.  Static axes and a 16 kHz input only (:27-28); any output rate."""
+    from . import nkf_aec
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    model_path = out_dir / f"{name}.adew"
+    save_blob(model_path, nkf_aec.state_to_blob_tensors(load_state_dict(checkpoint)))
+    write_metadata(model_path, nkf_aec.metadata(input_audio_length, out_sample_rate=out_sample_rate, input_audio_dtype=input_audio_dtype,
+                                                output_audio_dtype=output_audio_dtype, name=name))
+    return model_path
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     length, family, fold = None, "gtcrn", False
@@ -208,7 +223,7 @@ def main(argv=None) -> int:
             i = argv.index(flag)
             gt[key] = conv(argv[i + 1])
             del argv[i:i + 2]
-    if len(argv) != 2 or family not in ("gtcrn", "h_gtcrn", "mel_band_roformer", "mossformer2_ss", "ul_unas", "zipenhancer"):
+    if len(argv) != 2 or family not in ("gtcrn", "h_gtcrn", "mel_band_roformer", "mossformer2_ss", "ul_unas", "zipenhancer", "nkf_aec"):
         print(__doc__)
         return 2
     model_rate = 44100 if family == "mel_band_roformer" else 16000
@@ -227,6 +242,9 @@ def main(argv=None) -> int:
     elif family == "zipenhancer":
         path = export_zipenhancer(argv[0], argv[1], length or 32000, fold, dynamic_axes=gt["dynamic_axes"], in_sample_rate=gt["in_sample_rate"],
                                   out_sample_rate=gt["out_sample_rate"])
+    elif family == "nkf_aec":
+        path = export_nkf_aec(argv[0], argv[1], length or 32000, out_sample_rate=gt["out_sample_rate"], input_audio_dtype=gt["input_audio_dtype"],
+                              output_audio_dtype=gt["output_audio_dtype"])
     else:
         path = export_gtcrn(argv[0], argv[1], length or 16000, **gt)
     print(f"Export done: {path} (+ {path.with_name(path.stem + '_Metadata.json').name})")

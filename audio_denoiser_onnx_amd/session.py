@@ -22,6 +22,8 @@ from .metadata import MetadataReader, load_runtime_metadata, validate_audio_meta
 
 INPUT_NAME = "noisy_audio"       # GTCRN/Export_GTCRN.py:768
 OUTPUT_NAME = "denoised_audio"   # GTCRN/Export_GTCRN.py:769
+AEC_INPUT_NAMES = ("far_end_audio", "near_end_audio")   # NKF_AEC/Export_NKF_AEC.py:524-525
+AEC_OUTPUT_NAME = "aec_audio"
 
 
 class NodeArg:
@@ -90,9 +92,14 @@ class InferenceSession:
         self.in_dtype = {"INT16": np.int16, "F32": np.float32, "F16": np.float16}[reader.string("input_audio_dtype", "INT16")]
         self.out_dtype = {"INT16": np.int16, "F32": np.float32, "F16": np.float16}[reader.string("output_audio_dtype", "INT16")]
         tname = {np.int16: "tensor(int16)", np.float32: "tensor(float)", np.float16: "tensor(float16)"}
-        self._inputs = [NodeArg(in_name, [1, io.in_channels, io.in_len], tname[self.in_dtype])]
-        out_names = [OUTPUT_NAME] if io.n_outputs == 1 else [f"separated_{i}" for i in range(io.n_outputs)]   # Export_MossFormer2_SS_16K.py:689-690
+        self._aec = reader.string("model_family", "") == "nkf_aec"
+        if self._aec:      # two graph inputs (far end, near end), one channel each: channels 0 and 1 of the engine's planar rows (Export_NKF_AEC.py:524-525)
+            self._inputs = [NodeArg(n, [1, 1, io.in_len], tname[self.in_dtype]) for n in AEC_INPUT_NAMES]
+        else:
+            self._inputs = [NodeArg(in_name, [1, io.in_channels, io.in_len], tname[self.in_dtype])]
+        out_names = ([AEC_OUTPUT_NAME] if self._aec else [OUTPUT_NAME]) if io.n_outputs == 1 else [f"separated_{i}" for i in range(io.n_outputs)]   # Export_MossFormer2_SS_16K.py:689-690
         self._outputs = [NodeArg(name, [1, io.out_channels, io.out_len], tname[self.out_dtype]) for name in out_names]
+        self._planar_name = "far_end_near_end_audio"            # (internal: the interleaved two-input tensor of an AEC call)
         self._inputs_meta, self._outputs_meta = self._inputs, self._outputs   # names the reference script touches
         validate_audio_metadata(reader, self)
 
@@ -110,10 +117,24 @@ class InferenceSession:
         return ["AdeMI355XExecutionProvider"]
 
     def run(self, output_names, input_feed: Dict[str, np.ndarray], return_f32: bool = False):
-        """``session.run(None, {"noisy_audio": int16 (B,1,L)})`` -> ``[int16 (B,1,L_out)]`` (+ fp32 pre-PCM tap)."""
-        if self._inputs[0].name not in input_feed:
-            raise KeyError(f"missing input {self._inputs[0].name!r}")
-        x = np.asarray(input_feed[self._inputs[0].name])
+        """``session.run(None, {"noisy_audio": int16 (B,1,L)})`` -> ``[int16 (B,1,L_out)]`` (+ fp32 pre-PCM tap).
+        NKF-AEC: ``{"far_end_audio": (B,1,L), "near_end_audio": (B,1,L)}`` -> ``[aec_audio (B,1,L_out)]``."""
+        if self._aec:
+            parts = []
+            for arg in self._inputs:
+                if arg.name not in input_feed:
+                    raise KeyError(f"missing input {arg.name!r}")
+                a = np.asarray(input_feed[arg.name])
+                if a.ndim != 3 or a.shape[1] != 1 or a.shape[2] != self.in_len:
+                    raise ValueError(f"{arg.name} must have shape (B, 1, {self.in_len}), got {a.shape}")
+                parts.append(a)
+            if parts[0].shape[0] != parts[1].shape[0] or parts[0].dtype != parts[1].dtype:
+                raise ValueError("far_end_audio and near_end_audio must have the same batch size and dtype")
+            input_feed = {self._planar_name: np.concatenate(parts, axis=1)}      # planar (B, 2, L): far end, near end
+        name = self._planar_name if self._aec else self._inputs[0].name
+        if name not in input_feed:
+            raise KeyError(f"missing input {name!r}")
+        x = np.asarray(input_feed[name])
         if x.dtype != self.in_dtype:
             raise ValueError(f"{INPUT_NAME} must be {np.dtype(self.in_dtype).name}, got {x.dtype}")
         if x.ndim != 3 or x.shape[1] != self.channels or x.shape[2] != self.in_len:

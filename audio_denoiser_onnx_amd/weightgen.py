@@ -49,3 +49,9 @@ def tensor(name: str, shape: Sequence[int], scale: float, seed: int = 0) -> np.n
 
 def materialise(spec: Iterable[Tuple[str, Sequence[int], float]], seed: int = 0) -> Dict[str, np.ndarray]:
     return {name: tensor(name, shape, scale, seed) for name, shape, scale in spec}
+
+
+# NKF-AEC seeded weights (tools/make_golden_nkf_aec.py): PyTorch's default initialisation under torch.manual_seed(seed), with the Kalman-gain layer
+# fc_out_dense2 (weight and bias) multiplied by this factor.  The per-bin Kalman recurrence is only stable with a small gain: default init, or more than
+# about 0.03 x default on that layer, diverges (NaN or a 10 x output RMS), and fp32 evaluations of a diverging filter disagree by tens of LSB.
+NKF_GAIN_LAYER_SCALE = 1e-2
