@@ -915,6 +915,9 @@ struct ade_stream {
     int device = 0;
     int S = 0, N = 0;
     bool first = true, flushed = false;
+    // a sub-engine's stream (SubEngine::stream_*): the state is the sub-engine's, this object keeps the handle, the flags above and the host staging below
+    void* sub_state = nullptr;
+    int in_ch = 1, delay = kHop;     // PCM rows per stream and push; samples the output lags the input (= the flush length)
     int16_t *pcm_prev = nullptr, *pcm_hist = nullptr, *concat = nullptr, *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
     float *d_f32 = nullptr, *h_f32 = nullptr;
     float* state = nullptr;      // one allocation: dc | conv histories (ping-pong) | TRA hidden | inter-GRU hidden | OLA carry
@@ -2246,11 +2249,66 @@ ade_status ade_istft_forward(ade_handle h, const float* d_spec, int batch, int f
 
 
 // ---- streaming entry points ---------------------------------------------------------------------------------------------
+// A stream of a sub-engine (NKF-AEC): the sub-engine owns the carried state and the kernels (SubEngine::stream_*), this side the handle, the staging and the rules.
+static ade_status sub_stream_create(ade_handle h, int n_streams, int frames_per_push, ade_stream_handle* out) {
+    if (h->resample || h->n_win != 1)
+        return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: " + h->meta["model_family"] + " streams take int16 PCM in and out at the model rate (16000 Hz); this handle has float audio tensors, "
+                                            "another sample rate or batch-fold");
+    if (n_streams < 1 || frames_per_push < 1 || frames_per_push > 4096)
+        return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_create: need n_streams >= 1 and 1 <= frames_per_push <= 4096");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ade_stream* st = new ade_stream();
+    st->e = h; st->device = h->device; st->S = n_streams; st->N = frames_per_push;
+    st->in_ch = h->sub->stream_channels();
+    st->delay = h->sub->stream_delay();
+    h->live_streams.push_back(st);
+    std::string serr;
+    const int rc = h->sub->stream_create(n_streams, frames_per_push, &st->sub_state, serr);
+    if (rc != ADE_OK) {
+        ade_stream_destroy(st);
+        return fail(h, (ade_status)rc, serr);
+    }
+    const size_t S = (size_t)n_streams, P = (size_t)frames_per_push * kHop, n_in = S * st->in_ch * P, n_out = S * (P > (size_t)st->delay ? P : (size_t)st->delay);
+    if (hipMalloc((void**)&st->d_in, n_in * sizeof(int16_t)) != hipSuccess || hipMalloc((void**)&st->d_out, n_out * sizeof(int16_t)) != hipSuccess ||
+        hipMalloc((void**)&st->d_f32, n_out * sizeof(float)) != hipSuccess ||
+        hipHostMalloc((void**)&st->h_in, n_in * sizeof(int16_t), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&st->h_out, n_out * sizeof(int16_t), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&st->h_f32, n_out * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+        ade_stream_destroy(st);
+        return fail(h, ADE_ERR_DEVICE, "ade_stream_create: allocation of the PCM staging buffers failed");
+    }
+    const ade_status rs = ade_stream_reset(st);
+    if (rs != ADE_OK) {
+        ade_stream_destroy(st);
+        return rs;
+    }
+    *out = st;
+    return ADE_OK;
+}
+
+// push (d_in set) or flush (d_in null) of a sub-engine's stream on `s`
+static ade_status sub_stream_enqueue(ade_stream* st, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32) {
+    ade_engine* h = st->e;
+    std::string serr;
+    const int rc = d_in ? h->sub->stream_push(st->sub_state, s, d_in, d_out, d_f32, serr) : h->sub->stream_flush(st->sub_state, s, d_out, d_f32, serr);
+    if (rc != ADE_OK) return fail(h, (ade_status)rc, serr);
+    st->first = false;
+    return ADE_OK;
+}
+
+ade_status ade_stream_delay(ade_stream_handle st, int* samples) {
+    if (!st || !st->e || !samples) return ADE_ERR_BAD_VALUE;
+    *samples = st->delay;
+    return ADE_OK;
+}
+
 ade_status ade_stream_create(ade_handle h, int n_streams, int frames_per_push, ade_stream_handle* out) {
     if (!out) return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_create: out is NULL");
     *out = nullptr;
     if (!h) return ADE_ERR_BAD_VALUE;
-    if (h->sub || h->n_win != 1 || h->gt_sand) return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: streaming is implemented for plain GTCRN handles (int16 audio at the model rate)");
+    if (h->sub && h->sub->stream_delay() > 0) return sub_stream_create(h, n_streams, frames_per_push, out);
+    if (h->sub || h->n_win != 1 || h->gt_sand)
+        return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: streaming is implemented for plain GTCRN and NKF-AEC handles (int16 audio at the model rate)");
     if (n_streams < 1 || frames_per_push < 2 || frames_per_push > 4096)
         return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_create: need n_streams >= 1 and 2 <= frames_per_push <= 4096 (the first push reflects 257 samples)");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2340,6 +2398,15 @@ ade_status ade_stream_reset(ade_stream_handle st) {
     ade_engine* h = st->e;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (st->sub_state) {
+        std::string serr;
+        const int rc = h->sub->stream_reset(st->sub_state, h->stream, serr);
+        if (rc != ADE_OK) return fail(h, (ade_status)rc, serr);
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        st->first = true;
+        st->flushed = false;
+        return ADE_OK;
+    }
     HIP_TRY(h, hipMemset(st->state, 0, st->state_floats * sizeof(float)));
     HIP_TRY(h, hipMemset(st->pcm_hist, 0, (size_t)st->S * kHop * sizeof(int16_t)));
     HIP_TRY(h, hipMemset(st->pcm_prev, 0, (size_t)st->S * sizeof(int16_t)));
@@ -2362,7 +2429,12 @@ ade_status ade_stream_push_device(ade_stream_handle st, const int16_t* d_in, int
     if (st->flushed) return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_push: the stream was flushed; reset it first");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    enqueue_stream(st, s, d_in, d_out_pcm, d_out_f32);
+    if (st->sub_state) {
+        const ade_status rc = sub_stream_enqueue(st, s, d_in, d_out_pcm, d_out_f32);
+        if (rc != ADE_OK) return rc;
+    } else {
+        enqueue_stream(st, s, d_in, d_out_pcm, d_out_f32);
+    }
     HIP_TRY(h, hipGetLastError());
     if (!hip_stream) HIP_TRY(h, hipStreamSynchronize(s));
     return ADE_OK;
@@ -2373,10 +2445,15 @@ ade_status ade_stream_push(ade_stream_handle st, const int16_t* in, int16_t* out
     ade_engine* h = st->e;
     if (st->flushed) return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_push: the stream was flushed; reset it first");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)st->S * st->N * kHop;
-    memcpy(st->h_in, in, n * sizeof(int16_t));
-    HIP_TRY(h, hipMemcpyAsync(st->d_in, st->h_in, n * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
-    enqueue_stream(st, h->stream, st->d_in, st->d_out, out_f32 ? st->d_f32 : nullptr);
+    const size_t n = (size_t)st->S * st->N * kHop, n_in = n * st->in_ch;
+    memcpy(st->h_in, in, n_in * sizeof(int16_t));
+    HIP_TRY(h, hipMemcpyAsync(st->d_in, st->h_in, n_in * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    if (st->sub_state) {
+        const ade_status rc = sub_stream_enqueue(st, h->stream, st->d_in, st->d_out, out_f32 ? st->d_f32 : nullptr);
+        if (rc != ADE_OK) return rc;
+    } else {
+        enqueue_stream(st, h->stream, st->d_in, st->d_out, out_f32 ? st->d_f32 : nullptr);
+    }
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(st->h_out, st->d_out, n * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
     if (out_f32) HIP_TRY(h, hipMemcpyAsync(st->h_f32, st->d_f32, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2392,8 +2469,13 @@ ade_status ade_stream_flush(ade_stream_handle st, int16_t* out_pcm, float* out_f
     ade_engine* h = st->e;
     if (st->first || st->flushed) return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_flush: nothing to flush (no push since the last reset, or already flushed)");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)st->S * kHop;
-    enqueue_stream(st, h->stream, nullptr, st->d_out, out_f32 ? st->d_f32 : nullptr, /*flush=*/true);
+    const size_t n = (size_t)st->S * st->delay;
+    if (st->sub_state) {
+        const ade_status rc = sub_stream_enqueue(st, h->stream, nullptr, st->d_out, out_f32 ? st->d_f32 : nullptr);
+        if (rc != ADE_OK) return rc;
+    } else {
+        enqueue_stream(st, h->stream, nullptr, st->d_out, out_f32 ? st->d_f32 : nullptr, /*flush=*/true);
+    }
     st->flushed = true;
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(st->h_out, st->d_out, n * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
@@ -2409,6 +2491,8 @@ namespace {
 void release_stream_buffers(ade_stream* st) {
     (void)hipSetDevice(st->device);
     (void)hipDeviceSynchronize();
+    if (st->sub_state && st->e && st->e->sub) st->e->sub->stream_destroy(st->sub_state);     // (both callers run while the engine and its sub-engine are alive)
+    st->sub_state = nullptr;
     if (st->state) (void)hipFree(st->state);
     if (st->ws) (void)hipFree(st->ws);
     if (st->pcm_hist) (void)hipFree(st->pcm_hist);

@@ -272,6 +272,20 @@ struct SubEngine {
     // that nobody consumed).  xwait: the engine's option "xwait_ms" in 10 ns ticks.
     virtual int exchange_error_and_reset() { return 0; }
     virtual void set_exchange_wait_ticks(int) {}
+    // Stateful streaming (ade_stream_* in include/ade.h).  A sub-engine that streams owns its stream state behind an opaque pointer; the engine keeps the caller's handle,
+    // the host staging and the pushed / flushed bookkeeping and forwards here.  All pointers are device memory, everything is enqueued on `s` without a synchronise.
+    // stream_channels() PCM rows of frames_per_push * 256 samples in per stream, one row out; stream_delay() = samples the output lags the input = the flush length
+    // (0: the family does not stream).
+    virtual int stream_delay() const { return 0; }
+    virtual int stream_channels() const { return channels(); }
+    virtual int stream_create(int /*n_streams*/, int /*frames_per_push*/, void** /*state*/, std::string& err) {
+        err = "streaming is not implemented for this model family";
+        return 6;   // ADE_ERR_UNSUPPORTED
+    }
+    virtual int stream_reset(void* /*state*/, hipStream_t, std::string&) { return 6; }
+    virtual int stream_push(void* /*state*/, hipStream_t, const int16_t* /*d_in*/, int16_t* /*d_out*/, float* /*d_f32*/, std::string&) { return 6; }
+    virtual int stream_flush(void* /*state*/, hipStream_t, int16_t* /*d_out*/, float* /*d_f32*/, std::string&) { return 6; }
+    virtual void stream_destroy(void* /*state*/) {}
 };
 // model_family "dfsmn" (DFSMN/Export_DFSMN.py:71-246), csrc/ade_dfsmn.hip
 int dfsmn_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, int device, SubEngine** out, std::string& err);

@@ -19,6 +19,13 @@
 //   k_nkf_ola       overlap-add as a gather, trim [512 : 512 + 256 (T - 1)], * 1 / window-square sum (the f32 waveform) and * 32767 / sum -> .to(int16)
 //                   (:383-408); the [:audio_len] trim keeps min(L, 256 (T - 1)) samples.
 // The frame-0 branch of the reference (:309-335) is the general step with zero state, so one loop body serves every frame.
+//
+// Streams (ade_stream_* on an nkf_aec handle, include/ade.h): a push of F hops continues where the previous one stopped, four launches and no mean kernel --
+//   k_nkf_stream_analysis   rows [768 carried | P new]; the far-end and the near-end frame of the SAME index as one complex FFT; keeps the next carry
+//   k_nkf_kalman<true>      the same kernel, the 96 state floats of each lane loaded at entry and stored at exit ([96][streams * 513])
+//   k_nkf_stream_synthesis  one frame per transform, appended to the stream's last three windowed frames
+//   k_nkf_stream_ola        the gather over the covering frames with the window-square sum formed alongside, 768 samples behind the input
+// so that the result does not depend on the push size, bit for bit ("Streaming").
 #include "ade_fft.h"
 #include "ade_internal.h"
 #include "../../include/ade.h"
@@ -75,6 +82,18 @@ __device__ __forceinline__ CFloat* frame_weights(unsigned long long a) {
     return (CFloat*)(((unsigned long long)hi << 32) | lo);
 }
 __device__ __forceinline__ CFloat* frame_weights(const float* w) { return frame_weights((unsigned long long)w); }
+#endif
+// Column j of a stream's Kalman state, [kStateFloats][lanes].  The base is pinned to scalar registers at every use: left to itself the compiler forms the 96 per-lane
+// 64-bit addresses of the loads at kernel entry in vector registers and keeps every one of them alive, in 174 accumulator registers, for the stores at exit --
+// 430 registers, one wave per SIMD instead of two.
+#ifdef HIPSIM
+__device__ __forceinline__ float* state_column(float* state, size_t off) { return state + off; }
+#else
+__device__ __forceinline__ float* state_column(float* state, size_t off) {
+    unsigned long long a = (unsigned long long)(state + off);
+    __asm__ volatile("" : "+s"(a));
+    return (float*)a;
+}
 #endif
 __device__ __forceinline__ f2v ld2(CFloat* p) { return *reinterpret_cast<CF2*>(p); }
 __device__ __forceinline__ f2v splat(float w) { return f2v{w, w}; }
@@ -149,9 +168,13 @@ __global__ __launch_bounds__(256) void k_nkf_analysis(const int16_t* __restrict_
     }
 }
 
-// one lane per (call, bin): the whole Kalman recurrence of the call (:302-373)
+// one lane per (call, bin): the whole Kalman recurrence of the call (:302-373).  CARRY (streams): the lane's state -- xt, h_prior, h_post, the four GRU hidden vectors,
+// kStateFloats floats -- is loaded from `state` at entry and stored back at exit, laid out [kStateFloats][rows * kF] so that a wave's loads and stores of one
+// float are contiguous; T = 0 (a stream's first one-hop push) runs no frame and leaves the state as it was.  kg is an output of every frame and is not carried.
+constexpr int kStateFloats = 2 * (3 * kTaps + 2 * kHid);
+template <bool CARRY>
 __global__ __launch_bounds__(kKalmanThreads) void k_nkf_kalman(const float2* __restrict__ spec, const float* __restrict__ W0, int T, int rows,
-                                                              float2* __restrict__ err, float2* __restrict__ kg_last) {
+                                                              float2* __restrict__ err, float2* __restrict__ kg_last, float* __restrict__ state) {
     const int i = (int)blockIdx.x * kKalmanThreads + (int)threadIdx.x;
     if (i >= rows * kF) return;
     const int call = i / kF, f = i - call * kF;
@@ -165,6 +188,23 @@ __global__ __launch_bounds__(kKalmanThreads) void k_nkf_kalman(const float2* __r
     for (int k = 0; k < kTaps; ++k) { xt[k] = f2v{0.0f, 0.0f}; hp[k] = xt[k]; hq[k] = xt[k]; kg[k] = xt[k]; }
 #pragma unroll
     for (int k = 0; k < kHid; ++k) { hr[k] = f2v{0.0f, 0.0f}; hi[k] = hr[k]; }
+    // state float j of this lane: a wave-uniform column base (state_column: a scalar register pair) plus the lane's 32-bit index
+    const size_t sn = (size_t)rows * kF;
+    auto col = [&](int j) -> float* { return state_column(state, (size_t)j * sn); };
+    const unsigned lane = (unsigned)i;
+    if constexpr (CARRY) {
+#pragma unroll
+        for (int k = 0; k < kTaps; ++k) {
+            xt[k] = f2v{col(2 * k)[lane], col(2 * k + 1)[lane]};
+            hp[k] = f2v{col(2 * (kTaps + k))[lane], col(2 * (kTaps + k) + 1)[lane]};
+            hq[k] = f2v{col(2 * (2 * kTaps + k))[lane], col(2 * (2 * kTaps + k) + 1)[lane]};
+        }
+#pragma unroll
+        for (int k = 0; k < kHid; ++k) {
+            hr[k] = f2v{col(2 * (3 * kTaps + k))[lane], col(2 * (3 * kTaps + k) + 1)[lane]};
+            hi[k] = f2v{col(2 * (3 * kTaps + kHid + k))[lane], col(2 * (3 * kTaps + kHid + k) + 1)[lane]};
+        }
+    }
     for (int t = 0; t < T; ++t) {
         // the weight pointer laundered through an empty asm each frame: without it the compiler hoists all ~4.4 k uniform weights out of the frame loop into
         // SGPRs, spills them into VGPR lanes (1191 spills) and reads each back with v_readlane; this way they are re-fetched by scalar loads every frame
@@ -226,6 +266,110 @@ __global__ __launch_bounds__(kKalmanThreads) void k_nkf_kalman(const float2* __r
 #pragma unroll
         for (int l = 0; l < kTaps; ++l) kg_last[(size_t)i * kTaps + l] = make_float2(kg[l].x, kg[l].y);
     }
+    if constexpr (CARRY) {
+#pragma unroll
+        for (int k = 0; k < kTaps; ++k) {
+            col(2 * k)[lane] = xt[k].x; col(2 * k + 1)[lane] = xt[k].y;
+            col(2 * (kTaps + k))[lane] = hp[k].x; col(2 * (kTaps + k) + 1)[lane] = hp[k].y;
+            col(2 * (2 * kTaps + k))[lane] = hq[k].x; col(2 * (2 * kTaps + k) + 1)[lane] = hq[k].y;
+        }
+#pragma unroll
+        for (int k = 0; k < kHid; ++k) {
+            col(2 * (3 * kTaps + k))[lane] = hr[k].x; col(2 * (3 * kTaps + k) + 1)[lane] = hr[k].y;
+            col(2 * (3 * kTaps + kHid + k))[lane] = hi[k].x; col(2 * (3 * kTaps + kHid + k) + 1)[lane] = hi[k].y;
+        }
+    }
+}
+
+// ---- streams: a push of F hops continues the signal where the previous push stopped (include/ade.h, ade_stream_*) ---------------------------------------------
+// Frame t covers the samples [256 t - 512, 256 t + 512), so after k hops of input the frames 0 .. k - 2 exist.  A push reads rows [768 carried | P new] samples,
+// which start at sample 256 k - 768 (k = hops before the push): its first frame, t = k - 1, starts at row offset 0 (the stream's first push has no frame -1 and
+// starts with frame 0 at offset 256, its carry being the zeros of the constant centre pad).
+constexpr int kCarry = 3 * kHopN;
+
+// one workgroup per (stream, frame): the far-end and the near-end frame OF THE SAME INDEX as one complex transform.  Pairing frames (t, t + 1) as the one-shot
+// kernel does would make a frame's rounding depend on where the push boundary falls (the two halves of a packed transform share rounding cross-talk); the two
+// channels of a frame always arrive together.  The last workgroup of a stream (frame index T) moves the rows' last 768 samples into the OTHER carry buffer.
+// pcm null (flush): the new samples are zeros, no carry is kept.
+__global__ __launch_bounds__(256) void k_nkf_stream_analysis(const int16_t* __restrict__ pcm, const int16_t* __restrict__ carry_in, int16_t* __restrict__ carry_out, int P, int T,
+                                                             int off0, fft::Plan plan, const float2* __restrict__ tw, const float* __restrict__ win, float2* __restrict__ spec) {
+    __shared__ float2 A[kN];
+    __shared__ float2 Bf[kN];
+    const int tid = threadIdx.x, per = T + (carry_out ? 1 : 0), st = (int)blockIdx.x / per, j = (int)blockIdx.x - st * per;
+    auto row = [&](int ch, int p) -> int {                                  // sample p of the row [768 carried | P new] of channel ch
+        if (p < kCarry) return carry_in[((size_t)st * 2 + ch) * kCarry + p];
+        return pcm && p - kCarry < P ? pcm[((size_t)st * 2 + ch) * P + (p - kCarry)] : 0;
+    };
+    if (j == T) {
+        for (int n = tid; n < 2 * kCarry; n += 256) {
+            const int ch = n / kCarry, p = n - ch * kCarry;
+            carry_out[((size_t)st * 2 + ch) * kCarry + p] = (int16_t)row(ch, P + p);
+        }
+        return;
+    }
+    const int o = off0 + j * kHopN;
+    for (int n = tid; n < kN; n += 256) A[n] = make_float2((float)row(0, o + n) * win[n], (float)row(1, o + n) * win[n]);
+    const float2* r = fft::forward(A, Bf, plan, tw, tid, 256);
+    float2* far = spec + ((size_t)st * 2 * T + j) * kF;
+    float2* near = far + (size_t)T * kF;
+    for (int f = tid; f < kF; f += 256) {
+        const float2 z = r[f], zc = r[f == 0 ? 0 : kN - f];
+        far[f] = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y));
+        near[f] = make_float2(0.5f * (z.y + zc.y), 0.5f * (zc.x - z.x));
+    }
+}
+
+// The windowed frames of a stream live in rows of `slots` frames: [the last frames before this push | the push's frames from slot `base` on].  One workgroup per
+// (stream, slot): slots below `base` are copied from the OTHER buffer (slot prev_off + j there; zeros on the first push), the others are the inverse transform of
+// ONE error frame each -- no pairing, so a frame's bits do not depend on its neighbours in the push.
+__global__ __launch_bounds__(256) void k_nkf_stream_synthesis(const float2* __restrict__ err, int T, int base, int slots, const float* __restrict__ prev, int prev_off,
+                                                              fft::Plan plan, const float2* __restrict__ tw, const float* __restrict__ win, float* __restrict__ frames) {
+    __shared__ float2 A[kN];
+    __shared__ float2 Bf[kN];
+    const int tid = threadIdx.x, per = base + T, st = (int)blockIdx.x / per, j = (int)blockIdx.x - st * per;
+    float* dst = frames + ((size_t)st * slots + j) * kN;
+    if (j < base) {
+        const float* src = prev ? prev + ((size_t)st * slots + prev_off + j) * kN : nullptr;
+        for (int n = tid; n < kN; n += 256) dst[n] = src ? src[n] : 0.0f;
+        return;
+    }
+    const float2* s0 = err + ((size_t)st * T + (j - base)) * kF;
+    for (int f = tid; f < kF; f += 256) {
+        const bool edge = f == 0 || f == kF - 1;
+        const float2 a = s0[f];
+        const float im = edge ? 0.0f : a.y;
+        A[f] = make_float2(a.x, -im);
+        if (!edge) A[kN - f] = make_float2(a.x, im);
+    }
+    const float2* r = fft::forward(A, Bf, plan, tw, tid, 256);
+    for (int n = tid; n < kN; n += 256) dst[n] = r[n].x * (win[n] * (1.0f / (float)kN));
+}
+
+// Overlap-add of a push as a gather: output sample q of the push lies 768 samples behind the push's first input sample; slot j of the stream's frame row covers it at
+// n = q + 768 - 256 j.  The sum runs over the covering slots in [jmin, jmax] in ascending order (the order of k_nkf_ola) -- jmin: the slot of frame 0 while the
+// stream is younger than four hops, jmax: the last frame of the push, which only the flush reaches (the end of the signal) -- and so does the sum of the squared
+// window (win2 = fp32 hann^2, added in the same order as the one-shot table is built), so head, steady state and tail need no tables.  q < qmin: before the
+// stream's first sample, zero.
+__global__ __launch_bounds__(256) void k_nkf_stream_ola(const float* __restrict__ frames, const float* __restrict__ win2, int slots, int jmin, int jmax, int qmin, int P,
+                                                        int16_t* __restrict__ pcm, float* __restrict__ f32, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long st = i / P;
+    const int q = (int)(i - st * P);
+    float s = 0.0f, ws = 0.0f;
+    if (q >= qmin) {
+        int lo = q / kHopN, hi = lo + 3;
+        if (lo < jmin) lo = jmin;
+        if (hi > jmax) hi = jmax;
+        for (int j = lo; j <= hi; ++j) {
+            const int n = q + kCarry - j * kHopN;
+            s += frames[((size_t)st * slots + j) * kN + n];
+            ws += win2[n];
+        }
+    }
+    const bool live = ws > 0.0f;
+    if (f32) f32[i] = live ? s * (1.0f / ws) : 0.0f;
+    if (pcm) pcm[i] = live ? (int16_t)(int)fminf(fmaxf(s * (32767.0f / ws), -32768.0f), 32767.0f) : (int16_t)0;
 }
 
 // one workgroup per (call, frame pair): W = H(Z0) + i H(Z1) stored conjugated, x0 + i x1 = conj(DFT(conj W)) / N
@@ -297,6 +441,29 @@ struct NkfAecEngine : SubEngine {
     int reserve(int batch, std::string& err) override;
     int run(hipStream_t s, const int16_t* d_in, int batch, int16_t* d_out, float* d_f32, std::string& err) override;
     int tap(hipStream_t s, const char* name, int batch, float* out, size_t count, size_t* written, std::string& err) override;
+    // streams (ade_stream_*): state per stream object, see NkfStream below
+    const float* win2 = nullptr;                // fp32 hann^2, the terms of the window-square sum
+    int stream_delay() const override { return kCarry; }
+    int stream_create(int n_streams, int frames_per_push, void** state, std::string& err) override;
+    int stream_reset(void* state, hipStream_t s, std::string& err) override;
+    int stream_push(void* state, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) override;
+    int stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) override;
+    void stream_destroy(void* state) override;
+    int stream_step(struct NkfStream* st, hipStream_t s, const int16_t* d_in, int hops, int16_t* d_out, float* d_f32, std::string& err);
+};
+
+// What a stream carries between pushes, for S streams that advance together.
+struct NkfStream {
+    int S = 0, F = 0, slots = 0;                // streams, hops per push, frame slots per stream row (3 carried + the frames of the longest step)
+    long long hops = 0;                         // hops pushed since the last reset
+    int16_t* carry[2] = {};                     // [S][2][768] the last input samples of both channels, ping-ponged
+    int cur = 0;                                // carry[cur] / frames[cur] hold what the last step left
+    float* kalman = nullptr;                    // [kStateFloats][S * 513]
+    float* frames[2] = {};                      // [S][slots][1024] windowed frames, ping-ponged: the last three of a step are the head of the next one
+    int prev_off = 0;                           // slot of frames[cur] that becomes slot 0 of the next step
+    float2 *spec = nullptr, *errs = nullptr;    // one step's spectra [S][2][T][513] and error spectra [S][T][513]
+    void* block = nullptr;                      // the one allocation behind all of the above
+    size_t reset_bytes = 0;                     // its leading part that a reset clears (carries and Kalman state)
 };
 
 namespace {
@@ -353,8 +520,8 @@ int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int
     // periodic hann as torch.hann_window builds it in fp32; the 2^-15 input scale of an int16 export folded into the analysis window (:485)
     std::vector<float> hann(kN);
     for (int n = 0; n < kN; ++n) hann[n] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * n / kN));
-    const size_t o_wa = push(kN), o_win = push(kN), o_tw = push(2 * kN), o_iws = push(d->keep), o_iwp = push(d->keep);
-    for (int n = 0; n < kN; ++n) { arena[o_wa + n] = hann[n] * (1.0f / 32768.0f); arena[o_win + n] = hann[n]; }
+    const size_t o_wa = push(kN), o_win = push(kN), o_tw = push(2 * kN), o_iws = push(d->keep), o_iwp = push(d->keep), o_w2 = push(kN);
+    for (int n = 0; n < kN; ++n) { arena[o_wa + n] = hann[n] * (1.0f / 32768.0f); arena[o_win + n] = hann[n]; arena[o_w2 + n] = hann[n] * hann[n]; }
     for (int m = 0; m < kN; ++m) { const double a = -2.0 * M_PI * (double)m / (double)kN; arena[o_tw + 2 * m] = (float)cos(a); arena[o_tw + 2 * m + 1] = (float)sin(a); }
     {
         std::vector<float> wsum((size_t)kN + (size_t)kHopN * (d->T - 1), 0.0f);     // conv_transpose1d(ones, window^2) in fp32 (STFT_Process.py:242-249)
@@ -377,6 +544,7 @@ int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int
     d->inv_ws = d->d_w + o_iws;
     d->inv_ws_pcm = d->d_w + o_iwp;
     d->syn_win = d->d_w + o_win;
+    d->win2 = d->d_w + o_w2;
     *out = d;
     return ADE_OK;
 }
@@ -412,8 +580,8 @@ int NkfAecEngine::run(hipStream_t s, const int16_t* d_in, int batch, int16_t* d_
     const int ppr = (T + 1) / 2;
     hipLaunchKernelGGL(k_nkf_mean, dim3((unsigned)(batch * 2)), dim3(256), 0, s, d_in, float_in, L, mean);
     hipLaunchKernelGGL(k_nkf_analysis, dim3((unsigned)(batch * 2 * ppr)), dim3(256), 0, s, d_in, float_in, (const float*)mean, L, T, plan, tw, win, spec);
-    hipLaunchKernelGGL(k_nkf_kalman, dim3((unsigned)((batch * kF + kKalmanThreads - 1) / kKalmanThreads)), dim3(kKalmanThreads), 0, s, (const float2*)spec, wts, T, batch,
-                       errs, kg);
+    hipLaunchKernelGGL(k_nkf_kalman<false>, dim3((unsigned)((batch * kF + kKalmanThreads - 1) / kKalmanThreads)), dim3(kKalmanThreads), 0, s, (const float2*)spec, wts, T,
+                       batch, errs, kg, (float*)nullptr);
     hipLaunchKernelGGL(k_nkf_synthesis, dim3((unsigned)(batch * ppr)), dim3(256), 0, s, (const float2*)errs, T, plan, tw, syn_win, frames_buf);
     const long long total = (long long)batch * keep;
     hipLaunchKernelGGL(k_nkf_ola, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)frames_buf, inv_ws, inv_ws_pcm, T, keep, d_out, d_f32, total);
@@ -446,6 +614,90 @@ int NkfAecEngine::tap(hipStream_t s, const char* name, int batch, float* out, si
     }
     *written = n;
     return ADE_OK;
+}
+
+// ---- streams ----------------------------------------------------------------------------------------------------------------------------------------------------
+int NkfAecEngine::stream_create(int n_streams, int frames_per_push, void** state, std::string& err) {
+    *state = nullptr;
+    if (n_streams < 1 || frames_per_push < 1 || frames_per_push > 4096)
+        return nfail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: nkf_aec needs n_streams >= 1 and 1 <= frames_per_push <= 4096");
+    if ((long long)n_streams * kF > 0x7fffffffLL / 2 || (long long)n_streams * (frames_per_push + 1) * 2 > 0x7fffffffLL)
+        return nfail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: nkf_aec: n_streams * frames_per_push exceeds the launch grid");
+    NK_HIP(hipSetDevice(device));
+    NkfStream* st = new NkfStream();
+    st->S = n_streams;
+    st->F = frames_per_push;
+    const size_t S = (size_t)n_streams, Tm = (size_t)(frames_per_push > 2 ? frames_per_push : 2);      // the flush runs two frames
+    st->slots = (int)Tm + 3;
+    auto up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t b_carry = up(S * 2 * kCarry * sizeof(int16_t)), b_kal = up((size_t)kStateFloats * S * kF * sizeof(float)), b_fr = up(S * st->slots * kN * sizeof(float)),
+                 b_spec = up(S * 2 * Tm * kF * sizeof(float2)), b_err = up(S * Tm * kF * sizeof(float2));
+    if (hipMalloc(&st->block, 2 * b_carry + b_kal + 2 * b_fr + b_spec + b_err) != hipSuccess) {
+        delete st;
+        return nfail(err, ADE_ERR_DEVICE, "ade_stream_create: hipMalloc of the NKF-AEC stream state failed");
+    }
+    char* p = (char*)st->block;
+    st->carry[0] = (int16_t*)p; p += b_carry;
+    st->carry[1] = (int16_t*)p; p += b_carry;
+    st->kalman = (float*)p; p += b_kal;
+    st->reset_bytes = 2 * b_carry + b_kal;
+    st->frames[0] = (float*)p; p += b_fr;
+    st->frames[1] = (float*)p; p += b_fr;
+    st->spec = (float2*)p; p += b_spec;
+    st->errs = (float2*)p;
+    *state = st;
+    return ADE_OK;
+}
+
+int NkfAecEngine::stream_reset(void* state, hipStream_t s, std::string& err) {
+    NkfStream* st = (NkfStream*)state;
+    NK_HIP(hipMemsetAsync(st->block, 0, st->reset_bytes, s));     // the frame rows need no clearing: the first step writes its carried slots as zeros
+    st->hops = 0;
+    st->cur = 0;
+    st->prev_off = 0;
+    return ADE_OK;
+}
+
+// One step: `hops` new hops of input (d_in null: zeros past the end of the signal, the flush).  Analysis, Kalman, synthesis, overlap-add: four launches.
+int NkfAecEngine::stream_step(NkfStream* st, hipStream_t s, const int16_t* d_in, int hops, int16_t* d_out, float* d_f32, std::string& err) {
+    const bool first = st->hops == 0, flush = d_in == nullptr;
+    const int S = st->S, P = hops * kHopN, T = first ? hops - 1 : hops, base = first ? 4 : 3, nxt = st->cur ^ 1;
+    const int out = flush ? kCarry : P;                                                  // the flush emits the 768 samples still owed
+    const int young = st->hops < 4 ? (int)st->hops : 4;                                  // slot j holds frame hops - 4 + j
+    hipLaunchKernelGGL(k_nkf_stream_analysis, dim3((unsigned)(S * (T + (flush ? 0 : 1)))), dim3(256), 0, s, d_in, (const int16_t*)st->carry[st->cur],
+                       flush ? (int16_t*)nullptr : st->carry[nxt], P, T, first ? kHopN : 0, plan, tw, win, st->spec);
+    hipLaunchKernelGGL(k_nkf_kalman<true>, dim3((unsigned)((S * kF + kKalmanThreads - 1) / kKalmanThreads)), dim3(kKalmanThreads), 0, s, (const float2*)st->spec, wts, T, S,
+                       st->errs, (float2*)nullptr, st->kalman);
+    hipLaunchKernelGGL(k_nkf_stream_synthesis, dim3((unsigned)(S * (base + T))), dim3(256), 0, s, (const float2*)st->errs, T, base, st->slots,
+                       first ? (const float*)nullptr : (const float*)st->frames[st->cur], st->prev_off, plan, tw, syn_win, st->frames[nxt]);
+    const long long total = (long long)S * out;
+    hipLaunchKernelGGL(k_nkf_stream_ola, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)st->frames[nxt], win2, st->slots, 4 - young, base + T - 1,
+                       kCarry - young * kHopN > 0 ? kCarry - young * kHopN : 0, out, d_out, d_f32, total);
+    NK_HIP(hipGetLastError());
+    st->prev_off = base + T - 3;
+    st->cur = nxt;
+    st->hops += hops;
+    return ADE_OK;
+}
+
+int NkfAecEngine::stream_push(void* state, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) {
+    NkfStream* st = (NkfStream*)state;
+    return stream_step(st, s, d_in, st->F, d_out, d_f32, err);
+}
+
+// the last two frames (n - 1 and n after n hops), their samples past the end the zeros of the reference's constant centre pad
+int NkfAecEngine::stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) {
+    NkfStream* st = (NkfStream*)state;
+    if (st->hops == 0) return nfail(err, ADE_ERR_BAD_VALUE, "ade_stream_flush: nothing to flush");
+    return stream_step(st, s, nullptr, 2, d_out, d_f32, err);
+}
+
+void NkfAecEngine::stream_destroy(void* state) {
+    NkfStream* st = (NkfStream*)state;
+    if (!st) return;
+    (void)hipSetDevice(device);
+    if (st->block) (void)hipFree(st->block);
+    delete st;
 }
 
 }  // namespace ade

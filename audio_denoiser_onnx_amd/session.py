@@ -334,41 +334,62 @@ class StreamingSession:
     the causal-convolution histories and every GRU hidden state are carried on the device between pushes, so the concatenated outputs
     equal what the reference's graph computes on the whole signal in ONE call -- one hop (256 samples) later, the stream's first hop
     zero, and without the reference's whole-call DC removal (not causal).  The reference itself has no such mode: its driver calls a
-    stateless graph per slice (Inference_GTCRN_ONNX.py:307-317)."""
+    stateless graph per slice (Inference_GTCRN_ONNX.py:307-317).
+
+    On an NKF-AEC session the stream carries the echo canceller itself -- the per-bin Kalman state, the last 768 samples of the far-end and the near-end
+    signal and the ISTFT overlap -- so the filter keeps the echo path it has learnt across pushes.  ``in_channels`` is then 2 (far end, near end), ``push`` takes
+    ``(n_streams, 2, samples_per_push)`` (or ``push_aec(far, near)``), and ``delay`` is 768 samples: the outputs equal the reference's graph on the whole signal
+    in one call, 768 samples later.  ``delay`` is also the length of the flush; it is 256 for GTCRN."""
 
     def __init__(self, session: InferenceSession, n_streams: int, frames_per_push: int):
         self._lib, self._session = session._lib, session
         self.n_streams, self.frames_per_push, self.samples_per_push = int(n_streams), int(frames_per_push), int(frames_per_push) * 256
         self._h = C.c_void_p()
         self._lib.check(self._lib.c.ade_stream_create(session._h, self.n_streams, self.frames_per_push, C.byref(self._h)), session._h)
+        delay = C.c_int(0)
+        self._lib.check(self._lib.c.ade_stream_delay(self._h, C.byref(delay)), session._h)
+        self.delay = int(delay.value)
+        self.in_channels = 2 if getattr(session, "_aec", False) else 1
+        self._in_shape = (self.n_streams, 2, self.samples_per_push) if self.in_channels == 2 else (self.n_streams, self.samples_per_push)
+        self._out_shape = (self.n_streams, self.samples_per_push)
         import weakref
         if not hasattr(session, "_streams"):
             session._streams = []
         session._streams.append(weakref.ref(self))
 
     def push(self, pcm: np.ndarray, want_f32: bool = False):
-        """int16 (n_streams, samples_per_push) -> int16 of the same shape (+ fp32 pre-PCM waveform)."""
+        """int16 (n_streams, samples_per_push) -> int16 of the same shape (+ fp32 pre-PCM waveform).
+        NKF-AEC: int16 (n_streams, 2, samples_per_push), far end then near end -> int16 (n_streams, samples_per_push)."""
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
-        if pcm.shape != (self.n_streams, self.samples_per_push):
-            raise ValueError(f"expected int16 ({self.n_streams}, {self.samples_per_push}), got {pcm.shape}")
-        out = np.empty_like(pcm)
-        f32 = np.empty(pcm.shape, np.float32) if want_f32 else None
+        if pcm.shape != self._in_shape:
+            raise ValueError(f"expected int16 {self._in_shape}, got {pcm.shape}")
+        out = np.empty(self._out_shape, np.int16)
+        f32 = np.empty(self._out_shape, np.float32) if want_f32 else None
         st = self._lib.c.ade_stream_push(self._h, pcm.ctypes.data, out.ctypes.data, f32.ctypes.data if want_f32 else None)
         self._lib.check(st, self._session._h)
         return (out, f32) if want_f32 else out
 
+    def push_aec(self, far: np.ndarray, near: np.ndarray, want_f32: bool = False):
+        """NKF-AEC: two int16 (n_streams, samples_per_push) arrays, the far-end reference and the near-end microphone -> the echo-cancelled push."""
+        if self.in_channels != 2:
+            raise ValueError("push_aec needs a stream of an NKF-AEC session")
+        far, near = np.asarray(far), np.asarray(near)
+        if far.shape != self._out_shape or near.shape != self._out_shape:
+            raise ValueError(f"expected two int16 {self._out_shape} arrays, got {far.shape} and {near.shape}")
+        return self.push(np.stack([far, near], axis=1), want_f32)
+
     def push_device(self, d_in, d_out, d_f32=None, stream: Optional[int] = None) -> None:
-        if tuple(d_in.shape) != (self.n_streams, self.samples_per_push) or tuple(d_out.shape) != tuple(d_in.shape):
-            raise ValueError("device tensors must be (n_streams, samples_per_push) int16")
+        if tuple(d_in.shape) != self._in_shape or tuple(d_out.shape) != self._out_shape:
+            raise ValueError(f"device tensors must be int16 {self._in_shape} in and {self._out_shape} out")
         st = self._lib.c.ade_stream_push_device(self._h, C.c_void_p(d_in.data_ptr()), C.c_void_p(d_out.data_ptr()),
                                                 C.c_void_p(d_f32.data_ptr()) if d_f32 is not None else None, C.c_void_p(stream) if stream else None)
         self._lib.check(st, self._session._h)
 
     def flush(self, want_f32: bool = False):
         """End of the signal: the last hop, int16 (n_streams, 256).  ``concatenate(pushes + [flush])[:, 256:]`` is then exactly the one-shot
-        output of the whole signal.  ``reset()`` before pushing again."""
-        out = np.empty((self.n_streams, 256), np.int16)
-        f32 = np.empty((self.n_streams, 256), np.float32) if want_f32 else None
+        output of the whole signal.  ``reset()`` before pushing again.  In general the flush is ``delay`` samples long (768 for NKF-AEC)."""
+        out = np.empty((self.n_streams, self.delay), np.int16)
+        f32 = np.empty((self.n_streams, self.delay), np.float32) if want_f32 else None
         self._lib.check(self._lib.c.ade_stream_flush(self._h, out.ctypes.data, f32.ctypes.data if want_f32 else None), self._session._h)
         return (out, f32) if want_f32 else out
 

@@ -173,7 +173,7 @@ ade_status ade_istft_forward(ade_handle h, const float* d_spec, int batch, int f
  * on the whole signal in one call (every op of the network is causal in time), with two stated differences: the output is one
  * hop (256 samples, 16 ms) behind the input -- a frame is complete one hop after its centre -- with the stream's first hop zero;
  * and the per-call DC removal of GTCRN_CUSTOM.forward (Export_GTCRN.py:647, a mean over the WHOLE call, not computable causally)
- * is not applied.  GTCRN handles only (not batch-fold, not the other model families).  All streams of a handle advance together.
+ * is not applied.  Plain GTCRN handles (not batch-fold; of the other model families NKF-AEC streams, see below).  All streams of a handle advance together.
  * A push of up to 512 frames is ONE kernel launch (the fused chunk kernel continuing from the state its previous launch left); longer pushes, or a
  * stream created while the option "fused" is 0, take the multi-kernel sequence. */
 typedef struct ade_stream* ade_stream_handle;
@@ -188,6 +188,34 @@ ade_status ade_stream_push_device(ade_stream_handle s, const int16_t* d_in, int1
 ade_status ade_stream_flush(ade_stream_handle s, int16_t* out_pcm, float* out_f32);
 ade_status ade_stream_reset(ade_stream_handle s);      /* back to a fresh stream (zero state, next push reflects its head) */
 void ade_stream_destroy(ade_stream_handle s);           /* before ade_destroy of its engine */
+/* Samples the stream's output lags its input, which is also the flush length per stream: 256 for a GTCRN stream, 768 for an NKF-AEC stream. */
+ade_status ade_stream_delay(ade_stream_handle s, int* samples);
+
+/* ---- stateful streaming over the NKF-AEC path (model_family "nkf_aec"; the same entry points) -------------------------------
+ * An echo canceller is an adaptive filter: it is useful while it keeps the echo path it has learnt.  The one-shot call, like the
+ * reference's file driver, restarts every state at each slice, so the filter converges again every input_audio_length samples.
+ * A stream carries, per independent call: the last 768 input samples of each of the two channels, the Kalman state of each of the
+ * 513 bins (h_prior, h_post, the last 4 far-end frames, the four GRU hidden vectors: 96 floats) and the ISTFT overlap (the last
+ * three windowed frames).  Pushing a signal of n hops (n * 256 samples per channel) in pieces of frames_per_push * 256 samples and
+ * then flushing produces what the reference's graph (NKF.forward, Export_NKF_AEC.py:246-411, exported with
+ * INPUT_AUDIO_LENGTH = n * 256) produces on the whole signal in ONE call, with two stated differences:
+ *  1. The output is 768 samples (three hops, 48 ms) behind the input, and the stream's first 768 output samples are zero.  Frame t
+ *     covers the samples [256 t - 512, 256 t + 512), so after k hops of input the frames 0 .. k - 2 exist; output sample m sums the
+ *     frames up to m / 256 + 2, so 256 (k - 3) output samples are final.  The first push of F hops therefore runs F - 1 Kalman
+ *     frames, every later push F, and the flush the last two (frames n - 1 and n, zero-padded past the end as the reference's
+ *     constant centre pad does).
+ *  2. The per-call DC removal (:269, a mean over the whole call, not computable causally) is not applied -- as for GTCRN.
+ * Buffers: in [n_streams][2][frames_per_push * 256] int16 (far end, near end: the channel order of ade_process), out
+ * [n_streams][frames_per_push * 256] int16, out_f32 optional float of the same shape (the waveform before the PCM tail).
+ * ade_stream_flush returns the last 768 samples per stream (out [n_streams][768]), each divided by the window-square sum of the
+ * frames that cover it with T = n + 1 frames in all, i.e. the end-of-signal norm of the reference's static ISTFT (the engine sums
+ * the squared window over the covering frames in the order the one-shot table is built, so head, steady state -- 1.5 -- and tail
+ * are the same rule).  After a flush the stream must be reset before it is pushed again; ade_stream_reset returns to zero state.
+ * All streams of a handle advance together.  frames_per_push >= 1: the STFT pads with zeros, not a reflection, so a one-hop first
+ * push is legal (it runs no Kalman frame and returns zeros).  The result does not depend on the push size, bit for bit: every
+ * transform holds one frame index only (the far-end and near-end frame of index t in the analysis, one frame in the synthesis).
+ * Scope: int16 PCM in and out at 16 kHz; a handle with float audio tensors or another output rate answers ADE_ERR_UNSUPPORTED.
+ * ade_stream_push_device enqueues four kernels on the caller's stream and does not synchronise. */
 
 /* ---- generic STFT_Process operator: any n_fft / win_length / hop / window, for the other model families -------
  * Replaces the reference's STFT_Process module in its 'stft_B' (packed) and 'istft_B' (packed, static_norm=True) forms

@@ -13,6 +13,7 @@ rule the filter is stable and the echo path is exercised well above every tolera
 the blob (``nkf_aec_seed0.adew``) is ``audio_denoiser_onnx_amd.nkf_aec.state_to_blob_tensors`` of it, so the export round-trip test pins that mapping.
 
     python tools/make_golden_nkf_aec.py     # writes tests/golden/nkf_aec_seed0*.npz and nkf_aec_seed0.adew
+    python tools/make_golden_nkf_aec.py --stream     # writes tests/golden/nkf_aec_seed0_stream.npz only (the streaming tests' fixture)
 """
 import ast
 import os
@@ -172,5 +173,55 @@ def main(seed=0):
             print(fn, os.path.getsize(os.path.join(GOLD, fn)))
 
 
+STREAM_L = 49152            # 192 hops, T = 193.  Not longer: with the seeded weights the filter is only known stable this far (at 65 536 / offset 0 and at 96 000
+#                             it diverges, and two fp32 evaluations of a diverging filter disagree by the whole int16 range)
+
+
+def zero_sum(x):
+    """int16 signal -> the same signal with an EXACTLY zero integer sum (subtract sum // n, then one LSB from the first `sum` samples)."""
+    x = x.astype(np.int64)
+    x -= int(x.sum()) // len(x)
+    x[:int(x.sum())] -= 1
+    assert x.sum() == 0 and np.abs(x).max() < 32768
+    return x.astype(np.int16)
+
+
+def stream_fixture(seed=0):
+    """The streaming tests' reference: NKF.forward on 49 152 samples in ONE call, on inputs whose integer sum is exactly zero -- the reference's per-call DC
+    term is then exactly 0.0 and a stream (which cannot remove a whole-call mean) computes the same thing.  Writes nkf_aec_seed0_stream.npz and nothing else."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from nkf_aec_oracle import NkfAecOracle
+    ns = import_namespace(STREAM_L)
+    assert ns["MAX_SIGNAL_LENGTH"] == STREAM_L // 256 + 1 == 193
+    model, state = build(ns, seed)
+    committed = W.load_blob(os.path.join(GOLD, f"nkf_aec_seed{seed}.adew"))
+    for k, v in nkf_aec_state_to_blob_tensors(checkpoint_names(state)).items():
+        assert np.array_equal(v, committed[k]), f"seed-{seed} weights differ from the committed blob: {k}"
+    _, far_all, near_all = rows()
+    oracle = NkfAecOracle(committed, tables="exact")
+    fix = {}
+    for i, o in enumerate((48000, 160000)):
+        f, n = zero_sum(far_all[o:o + STREAM_L]), zero_sum(near_all[o:o + STREAM_L])
+        pair = torch.from_numpy(np.stack([f, n])).reshape(2, 1, -1).float()
+        mean = pair.mean(dim=2)                                                                  # the reference's own DC term (:269), in fp32
+        assert float(mean.abs().max()) == 0.0, f"clip {i}: the reference's fp32 mean is {mean.flatten().tolist()}, not 0"
+        pcm, istft, _ = run(model, f, n)
+        wave = (istft[:STREAM_L].astype(np.float64) / 32767.0).astype(np.float32)
+        opcm, owave, _ = oracle.forward(f[None], n[None])
+        d_pcm = int(np.abs(opcm[0].astype(np.int32) - pcm.astype(np.int32)).max())
+        d_wave = float(np.abs(owave[0] - wave).max())
+        print(f"clip {i} (offset {o}): max |out| {int(np.abs(pcm.astype(np.int32)).max())}  rms near {np.sqrt(np.mean((n / 32768.0) ** 2)):.4f}  "
+              f"rms(out - near) {np.sqrt(np.mean(((pcm.astype(np.float64) - n) / 32768.0) ** 2)):.4f}  oracle vs reference: {d_pcm} LSB, wave {d_wave:.2e}")
+        if d_pcm > 1 or d_wave > 1e-4:
+            raise SystemExit("oracle and reference disagree by more than 1 LSB / 1e-4: the filter is not stable on this clip, no fixture written")
+        fix[f"far{i}"], fix[f"near{i}"], fix[f"out{i}"], fix[f"wave{i}"] = f, n, pcm.astype(np.int16), wave
+    path = os.path.join(GOLD, f"nkf_aec_seed{seed}_stream.npz")
+    np.savez_compressed(path, **fix)
+    print(os.path.basename(path), os.path.getsize(path))
+
+
 if __name__ == "__main__":
-    main()
+    if "--stream" in sys.argv:
+        stream_fixture()
+    else:
+        main()
