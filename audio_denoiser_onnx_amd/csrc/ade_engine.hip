@@ -1041,10 +1041,12 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
     const bool fam_dfsmn = e->meta["model_family"] == "dfsmn", fam_melband = e->meta["model_family"] == "mel_band_roformer",
                fam_moss = e->meta["model_family"] == "mossformer2_ss", fam_ulu = e->meta["model_family"] == "ul_unas",
                fam_hg = e->meta["model_family"] == "h_gtcrn", fam_zip = e->meta["model_family"] == "zipenhancer",
-               fam_nkf = e->meta["model_family"] == "nkf_aec";
+               fam_nkf = e->meta["model_family"] == "nkf_aec", fam_dfa = e->meta["model_family"] == "dfsmn_aec";
     if (fam_nkf && !ade::nkf_aec_create)            // a library linked without csrc/ade_nkf_aec.hip (weak symbol)
         return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'nkf_aec' is not built into this library"));
-    if (fam_dfsmn || fam_melband || fam_moss || fam_ulu || fam_hg || fam_zip || fam_nkf) {   // DFSMN/Export_DFSMN.py (48 kHz mono) / Mel_Band_Roformer/Stereo/Export_MelBandRoformer.py (44.1 kHz stereo)
+    if (fam_dfa && (!ade::dfsmn_aec_create || !ade::nkf_backend_create))     // a library linked without csrc/ade_dfsmn_aec.hip / ade_nkf_aec.hip (weak symbols)
+        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'dfsmn_aec' is not built into this library"));
+    if (fam_dfsmn || fam_melband || fam_moss || fam_ulu || fam_hg || fam_zip || fam_nkf || fam_dfa) {   // DFSMN/Export_DFSMN.py (48 kHz mono) / Mel_Band_Roformer/Stereo/Export_MelBandRoformer.py (44.1 kHz stereo)
         const std::string fam = e->meta["model_family"];
         const long rate = fam_dfsmn ? 48000 : fam_melband ? 44100 : 16000;
         bool dyn_d = false, fold_d = false;
@@ -1074,6 +1076,20 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                 !opt("center_pad", "1"))
                 return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: STFT configuration other than 1024/1024/256 hann constant centre-pad"));
         }
+        if (fam_dfa) {      // DFSMN-AEC: the NKF back end and the one set of transforms the graph is built from (Export_DFSMN_AEC.py:39-60, :85-87, :101-110)
+            if (dyn_d) return bail(fail(e, ADE_ERR_UNSUPPORTED, "dfsmn_aec: dynamic_axes=1 does not exist with the NKF back end (Export_DFSMN_AEC.py:85-87 forces it off)"));
+            auto lam = e->meta.find("light_aec_model");
+            if (lam == e->meta.end() || lam->second != "NKF")
+                return bail(fail(e, ADE_ERR_UNSUPPORTED, "dfsmn_aec: light_aec_model must be NKF (got '" + (lam == e->meta.end() ? std::string() : lam->second) +
+                                                         "'; the SDAEC and Deep_Echo back ends are not implemented)"));
+            auto opt = [&](const char* k, const char* want) { auto it = e->meta.find(k); return it == e->meta.end() || it->second.empty() || it->second == want; };
+            struct { const char *k, *want; } cfg[] = {{"nfft", "640"}, {"window_length", "640"}, {"hop_length", "320"}, {"window_type", "hamming_symmetric"}, {"center_pad", "0"},
+                                                      {"pad_mode", "constant"}, {"nfft_a", "1024"}, {"nfft_a2", "640"}, {"window_length_a", "640"}, {"hop_length_a", "320"},
+                                                      {"nfft_b", "1024"}, {"window_length_b", "1024"}, {"hop_length_b", "256"}, {"window_type_b", "hann"}, {"n_mels", "80"}};
+            for (auto& c : cfg)
+                if (!opt(c.k, c.want))
+                    return bail(fail(e, ADE_ERR_UNSUPPORTED, std::string("dfsmn_aec: ") + c.k + " must be " + c.want + " (got '" + e->meta[c.k] + "')"));
+        }
         if (dyn_d && !fam_sand && !dyn_sf && !fam_hg)
             return bail(fail(e, ADE_ERR_UNSUPPORTED, "dynamic_axes=1 is not implemented for " + fam));
         if (e->meta.count("use_batch_fold") && !e->meta["use_batch_fold"].empty() && !parse_bool(e->meta["use_batch_fold"], &fold_d))
@@ -1082,6 +1098,11 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         // (windows, 36, F) activations as if there were one window, which interleaves the real and imaginary channel groups of neighbouring windows.
         if (fold_d && fam_nkf)
             return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: use_batch_fold=1 is not implemented (the reference's folded graph mixes the windows' channels)"));
+        if (fold_d && fam_dfa) {     // a folded window must reconstruct itself through the hop-320 mask ISTFT and hold a back-end frame (Export_DFSMN_AEC.py:118-120)
+            long fw = 0;
+            if (!e->meta.count("fold_window_length") || !parse_int(e->meta["fold_window_length"], &fw) || fw < 1024 || fw % 320)
+                return bail(fail(e, ADE_ERR_UNSUPPORTED, "dfsmn_aec: use_batch_fold=1 needs fold_window_length: a multiple of the 320-sample mask hop, at least 1024"));
+        }
         if (fold_d && fam_dfsmn) {   // a folded window must reconstruct itself: raw overlap-add length 1920 + 960 (T - 1) == W  (Export_DFSMN.py:54)
             long fw = 0;
             if (!e->meta.count("fold_window_length") || !parse_int(e->meta["fold_window_length"], &fw) || fw < 1920 || fw % 960)
@@ -1097,13 +1118,13 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         // is GTCRN's sandwich (down-sampling before the * 32767, up-sampling after it, :391-406).
         if (fam_nkf && sri != srm)
             return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: in_sample_rate must be the model rate, 16000 Hz (the static export sizes its ISTFT from the input-rate length)"));
-        const bool sand_out = fam_sand || fam_nkf;          // families whose output edge is the scale-factor sandwich
+        const bool sand_out = fam_sand || fam_nkf || fam_dfa;          // families whose output edge is the scale-factor sandwich (DFSMN-AEC: Export_DFSMN_AEC.py:1328-1343)
         // Resampling edges exist where the reference's STATIC export is self-consistent: MossFormer2 and DFSMN size their frames from the
         // model-rate length (Export_MossFormer2_SS_16K.py:36-37,99-104; Export_DFSMN.py:48,67).  Mel-Band-Roformer (like GTCRN) and UL-UNAS size
         // the static frame count from the INPUT-rate length (Export_MelBandRoformer.py:52), which only agrees with the STFT at equal rates.
         // H-GTCRN's static export is consistent too (frames from MODEL_AUDIO_LENGTH, Export_H_GTCRN.py:45-46); it interpolates by SCALE FACTOR.
         // ZipEnhancer sizes its frames from MODEL_AUDIO_LENGTH too (Export_ZipEnhancer.py:55, 61) and interpolates by size (:826-832, :905-911).
-        if (rates_differ && !fam_moss && !fam_dfsmn && !fam_hg && !fam_zip && !fam_nkf && !(fam_sand && dyn_d))
+        if (rates_differ && !fam_moss && !fam_dfsmn && !fam_hg && !fam_zip && !fam_nkf && !fam_dfa && !(fam_sand && dyn_d))
             return bail(fail(e, ADE_ERR_UNSUPPORTED, fam + " runs at " + std::to_string(rate) + " Hz in, model and out (its static export has no consistent resampling path" +
                                                      (fam_sand ? ": export with dynamic_axes=1 for other rates)" : ")")));
         if (dyn_d && fold_d) return bail(fail(e, ADE_ERR_BAD_VALUE, "Batch folding requires a static shape (dynamic_axes=0)."));     // (Export_MelBandRoformer.py:46)
@@ -1124,6 +1145,10 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                  : fam_melband ? (long)floor((double)caller_len * ((double)srm / (double)sri))       // F.interpolate(scale_factor = float(MODEL / IN)) (Export_MelBandRoformer.py:52, 631-644)
                  : fam_ulu ? (long)floor((double)caller_len * (1.0 / ((double)sri / 16000.0)))       // scale_factor = 1 / (in_sample_rate / 16000.0) (Export_UL_UNAS.py:835-837, 852-868)
                         : (long)nearbyint((double)caller_len * (double)srm / (double)sri)   /* Python round(): half to even */;
+            // DFSMN-AEC sizes its static graph from round(L * model / in) (Export_DFSMN_AEC.py:171-172) but interpolates by scale factor (:1192-1206), which yields
+            // floor(L * factor) samples: the export only exists where the two agree
+            if (fam_dfa && Ld != (long)floor((double)caller_len * (1.0 / ((double)sri / 16000.0))))
+                return bail(fail(e, ADE_ERR_SHAPE_MISMATCH, "dfsmn_aec: input_audio_length does not resample to a whole model-rate length"));
         }
         if (fold_d) {   // the graph input is ceil(L / W) whole windows of W model-rate samples, folded into the batch inside the model
             long fw = 0;    //                                                            (Export_MelBandRoformer.py:47-51, 644-647)
@@ -1174,6 +1199,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                        : fam_hg      ? ade::hgtcrn_create(e->tensors, (int)Ld, (int)sub_win, dyn_d, device, &e->sub, derr)
                        : fam_zip     ? ade::zipenhancer_create(e->tensors, (int)Ld, (int)sub_win, exact_dft, gemm_bf16, dyn_d, device, &e->sub, derr)
                        : fam_nkf     ? ade::nkf_aec_create(e->tensors, (int)Ld, device, &e->sub, derr)
+                       : fam_dfa     ? ade::dfsmn_aec_create(e->tensors, (int)Ld, (int)sub_win, exact_dft, device, &e->sub, derr)
                                      : ade::mossformer_create(e->tensors, (int)Ld, (int)sub_win, dyn_d, device, &e->sub, derr);
         if (rc != ADE_OK) return bail(fail(e, (ade_status)rc, derr));
         e->channels = e->sub->channels();
@@ -1210,7 +1236,8 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                 e->sub->float_src_len = (int)caller_len;
             } else if (sand_out) {   // scale_factor on both edges; down-sampling precedes the * 32767 of an int16 output, up-sampling follows it (Export_MelBandRoformer.py:660-680,
                 //                                                                                                                     Export_UL_UNAS.py:890-905)
-                const double f_in = fam_ulu ? 1.0 / ((double)sri / 16000.0) : (double)srm / (double)sri, f_out = fam_ulu ? (double)sro / 16000.0 : (double)sro / (double)srm;
+                const bool sf16 = fam_ulu || fam_dfa;      // scale factors written against 16000.0 (Export_UL_UNAS.py:835-837; Export_DFSMN_AEC.py:1142-1144)
+                const double f_in = sf16 ? 1.0 / ((double)sri / 16000.0) : (double)srm / (double)sri, f_out = sf16 ? (double)sro / 16000.0 : (double)sro / (double)srm;
                 out_caller = sro == srm ? (long)e->rs_model_out : (long)floor((double)e->rs_model_out * f_out);
                 e->rs_scale_in = sri == srm ? 1.0f : (float)(1.0 / f_in);
                 e->rs_scale_out = sro == srm ? 0.0f : (float)(1.0 / f_out);
@@ -1230,6 +1257,10 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         e->sample_rate = (int)rate;
         e->in_rate = (int)sri;
         e->out_rate = (int)sro;
+        if (fam_dfa) {      // ADE_GRAPH=0: plain launches instead of the captured graph (the option "graph" does the same per handle)
+            const char* genv = getenv("ADE_GRAPH");
+            if (genv && genv[0] == '0') e->use_graph = false;
+        }
         e->blob_storage.clear();
         e->blob_storage.shrink_to_fit();
         e->tensors.clear();
@@ -1237,7 +1268,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         return ADE_OK;
     }
     if (e->meta["model_family"] != "gtcrn")
-        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family '" + e->meta["model_family"] + "' is not implemented (gtcrn, h_gtcrn, dfsmn, mel_band_roformer, mossformer2_ss, ul_unas, zipenhancer, nkf_aec)"));
+        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family '" + e->meta["model_family"] + "' is not implemented (gtcrn, h_gtcrn, dfsmn, mel_band_roformer, mossformer2_ss, ul_unas, zipenhancer, nkf_aec, dfsmn_aec)"));
     bool dyn = false;
     if (!parse_bool(e->meta["dynamic_axes"], &dyn))
         return bail(fail(e, ADE_ERR_BAD_VALUE, "Metadata key dynamic_axes must be a boolean encoded as 1/0, got '" + e->meta["dynamic_axes"] + "'."));

@@ -302,5 +302,19 @@ int melband_create(const std::map<std::string, Tensor>& tensors, int window_len,
 // model_family "nkf_aec" (NKF_AEC/Export_NKF_AEC.py:150-411), csrc/ade_nkf_aec.hip.  Weak: a library linked without that source (the host simulator's fixed
 // source list) resolves it to null, and the engine answers ADE_ERR_UNSUPPORTED for the family.
 int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int device, SubEngine** out, std::string& err) __attribute__((weak));
+// The same filter as the linear back end of another family (dfsmn_aec): the analysis / Kalman / synthesis / overlap-add launches of csrc/ade_nkf_aec.hip without that
+// family's edges -- no DC removal, the raw overlap-add samples [512, 512 + window_len) with the matching slice of the static window-square table, a float waveform
+// left in device memory.  pcm / fpcm rows are [call][channel 0 = near end, channel 1 = far end][n_win windows of window_len] (fpcm: floats in int16 units, as
+// SubEngine::float_in); every window is an independent filter.  wave: [calls * n_win][window_len].
+struct NkfBackend {
+    virtual ~NkfBackend() {}
+    virtual int frames() const = 0;
+    virtual int reserve(int windows, std::string& err) = 0;
+    virtual int run(hipStream_t s, const int16_t* pcm, const float* fpcm, int calls, int n_win, float* wave, std::string& err) = 0;
+};
+// reference_tables: the two transforms as dense products with the reference's fp32-angle DFT tables instead of the FFT kernels (see csrc/ade_nkf_aec.hip, DenseFrameB).
+int nkf_backend_create(const std::map<std::string, Tensor>& tensors, int window_len, bool reference_tables, int device, NkfBackend** out, std::string& err) __attribute__((weak));
+// model_family "dfsmn_aec" with light_aec_model NKF (DFSMN_AEC/Export_DFSMN_AEC.py:897-1352), csrc/ade_dfsmn_aec.hip.  Weak, as nkf_aec_create.
+int dfsmn_aec_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, bool exact_dft /* ade_dft_tables = exact: the back end's FFT kernels */, int device, SubEngine** out, std::string& err) __attribute__((weak));
 
 }  // namespace ade

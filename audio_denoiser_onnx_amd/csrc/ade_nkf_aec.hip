@@ -27,6 +27,7 @@
 //   k_nkf_stream_ola        the gather over the covering frames with the window-square sum formed alongside, 768 samples behind the input
 // so that the result does not depend on the push size, bit for bit ("Streaming").
 #include "ade_fft.h"
+#include "ade_gemm.h"
 #include "ade_internal.h"
 #include "../../include/ade.h"
 
@@ -145,14 +146,18 @@ __global__ __launch_bounds__(256) void k_nkf_mean(const int16_t* __restrict__ pc
 }
 
 // one workgroup per (call, channel, frame pair): Z = FFT(a + i b), A[f] = (Z[f] + conj Z[N - f]) / 2, B[f] = (Z[f] - conj Z[N - f]) / (2 i)
+// n_win / swap (the back end of dfsmn_aec, nkf_backend_create): the source rows are [call][channel][n_win windows of L]; row = (call * n_win + window) * 2 + channel
+// reads source channel 1 - channel when swap is set (that family's channel 0 is the near end).  mean null: no DC removal.
 __global__ __launch_bounds__(256) void k_nkf_analysis(const int16_t* __restrict__ pcm, const float* __restrict__ fpcm, const float* __restrict__ mean, int L, int T,
-                                                      fft::Plan plan, const float2* __restrict__ tw, const float* __restrict__ win, float2* __restrict__ spec) {
+                                                      fft::Plan plan, const float2* __restrict__ tw, const float* __restrict__ win, float2* __restrict__ spec,
+                                                      int n_win, int swap) {
     __shared__ float2 A[kN];
     __shared__ float2 Bf[kN];
     const int tid = threadIdx.x, ppr = (T + 1) / 2, row = (int)blockIdx.x / ppr, t0 = 2 * ((int)blockIdx.x - row * ppr);
     const bool two = t0 + 1 < T;
-    const float m = mean[row];
-    const size_t base = (size_t)row * L;
+    const float m = mean ? mean[row] : 0.0f;
+    const int wrow = row >> 1, ch = swap ? 1 - (row & 1) : (row & 1), call = wrow / n_win;
+    const size_t base = (((size_t)call * 2 + ch) * n_win + (wrow - call * n_win)) * L;
     auto sample = [&](int t, int n) {
         const int p = t * kHopN + n - kN / 2;
         if (p < 0 || p >= L) return 0.0f;                               // centre pad with zeros, after the mean is removed (:269, :278)
@@ -412,6 +417,42 @@ __global__ __launch_bounds__(256) void k_nkf_ola(const float* __restrict__ frame
     if (pcm) pcm[i] = (int16_t)(int)fminf(fmaxf(s * inv_ws_pcm[m], -32768.0f), 32767.0f);     // .to(torch.int16): truncation (:407-408)
 }
 
+// ---- the back end's transforms with the REFERENCE's tables (nkf_backend_create, reference_tables): STFT_Process builds its windowed DFT kernels from fp32 angles
+// fl(fl(2 pi / N * f) * t) (DFSMN_AEC/STFT_Process.py:212-251), up to 3200 rad where half an ulp is 1.2e-4 rad.  A consumer that takes the logarithm of a difference
+// of spectra (dfsmn_aec's echo band) amplifies that angle error beyond 1 LSB of its output, so there the two transforms are dense products with tables built the same way,
+// on the matrix cores (csrc/ade_gemm.h); the Kalman kernel between them is the same launch either way.
+struct DenseFrameB {           // B(k, n): sample k of frame n = row * T + t, zero in the constant centre pad, * 2^-15
+    static constexpr bool kAlongN = false;
+    const int16_t* pcm;
+    const float* fpcm;
+    int L, T, n_win, swap;
+    __device__ float operator()(int k, int n) const {
+        const int row = n / T, t = n - row * T, p = t * kHopN + k - kN / 2;
+        if (p < 0 || p >= L) return 0.0f;
+        const int wrow = row >> 1, ch = swap ? 1 - (row & 1) : (row & 1), call = wrow / n_win;
+        const size_t at = (((size_t)call * 2 + ch) * n_win + (wrow - call * n_win)) * L + p;
+        return (fpcm ? fpcm[at] : (float)pcm[at]) * (1.0f / 32768.0f);
+    }
+};
+struct DenseSpecStore {        // rows 0 .. 512 the real parts, 513 .. 1025 the imaginary parts -> [frame][bin] (re, im)
+    float* spec;
+    __device__ void operator()(int m, int n, float v) const { spec[((size_t)n * kF + (m < kF ? m : m - kF)) * 2 + (m >= kF ? 1 : 0)] = v; }
+};
+struct DenseInvA {             // A(j, k) = inverse table row k (packed re | im bins), sample j
+    static constexpr bool kAlongK = false;
+    const float* p;
+    __device__ float operator()(int m, int k) const { return p[(size_t)k * kN + m]; }
+};
+struct DenseErrB {             // B(k, n) = packed [re bins | im bins] of error frame n
+    static constexpr bool kAlongN = false;
+    const float* e;
+    __device__ float operator()(int k, int n) const { return e[((size_t)n * kF + (k < kF ? k : k - kF)) * 2 + (k >= kF ? 1 : 0)]; }
+};
+struct DenseFrameStore {
+    float* p;
+    __device__ void operator()(int m, int n, float v) const { p[(size_t)n * kN + m] = v; }
+};
+
 }  // namespace
 
 struct NkfAecEngine : SubEngine {
@@ -450,6 +491,8 @@ struct NkfAecEngine : SubEngine {
     int stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) override;
     void stream_destroy(void* state) override;
     int stream_step(struct NkfStream* st, hipStream_t s, const int16_t* d_in, int hops, int16_t* d_out, float* d_f32, std::string& err);
+    const float *dense_fwd = nullptr, *dense_inv = nullptr;      // [1026][1024] each, the reference's fp32-angle tables (back end with reference_tables only)
+    int run_backend(hipStream_t s, const int16_t* pcm, const float* fpcm, int calls, int n_win, float* wave, std::string& err);
 };
 
 // What a stream carries between pushes, for S streams that advance together.
@@ -475,7 +518,9 @@ int nfail(std::string& err, int st, const std::string& msg) { err = msg; return 
     } while (0)
 }  // namespace
 
-int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int device, SubEngine** out, std::string& err) {
+// backend: the linear canceller of another family (nkf_backend_create) -- the ISTFT keeps the raw overlap-add samples [512, 512 + in_len) and the matching slice of
+// the static window-square table (the folder's istft_B_packed with output_length, DFSMN_AEC/STFT_Process.py:174-176, :256-266)
+static int nkf_build(const std::map<std::string, Tensor>& tensors, int in_len, int device, bool backend, bool reference_tables, NkfAecEngine** out, std::string& err) {
     *out = nullptr;
     if (in_len < kHopN) return nfail(err, ADE_ERR_SHAPE_MISMATCH, "nkf_aec: input_audio_length shorter than one 256-sample hop");
     struct Want { const char* name; std::vector<int> dims; const float* p; };
@@ -517,6 +562,7 @@ int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int
     d->L = in_len;
     d->T = in_len / kHopN + 1;                                       // MAX_SIGNAL_LENGTH (:35)
     d->keep = kHopN * (d->T - 1) < in_len ? kHopN * (d->T - 1) : in_len;     // the ISTFT's trimmed length, then [:audio_len] (:389)
+    if (backend) d->keep = in_len;                                   // 512 + in_len <= 1024 + 256 (T - 1): inside the raw overlap-add
     // periodic hann as torch.hann_window builds it in fp32; the 2^-15 input scale of an int16 export folded into the analysis window (:485)
     std::vector<float> hann(kN);
     for (int n = 0; n < kN; ++n) hann[n] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * n / kN));
@@ -532,6 +578,22 @@ int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int
             arena[o_iwp + m] = 32767.0f / wsum[kN / 2 + m];
         }
     }
+    size_t o_df = 0, o_di = 0;
+    if (backend && reference_tables) {
+        o_df = push((size_t)2 * kF * kN);
+        o_di = push((size_t)2 * kF * kN);
+        const float c32 = (float)(2.0 * M_PI / kN);
+        for (int f = 0; f < kF; ++f) {
+            const float cf = c32 * (float)f, sc = (f == 0 || f == kF - 1) ? 1.0f : 2.0f;
+            for (int t = 0; t < kN; ++t) {
+                const float om = cf * (float)t, c = cosf(om), sn = sinf(om);
+                arena[o_df + (size_t)f * kN + t] = c * hann[t];
+                arena[o_df + (size_t)(kF + f) * kN + t] = -sn * hann[t];
+                arena[o_di + (size_t)f * kN + t] = (sc * c * (1.0f / (float)kN)) * hann[t];
+                arena[o_di + (size_t)(kF + f) * kN + t] = (sc * -sn * (1.0f / (float)kN)) * hann[t];
+            }
+        }
+    }
     if (!fft::make_plan(kN, &d->plan)) { delete d; return nfail(err, ADE_ERR_UNSUPPORTED, "nkf_aec: FFT plan"); }
     auto bail = [&](int st) { delete d; return st; };
     if (hipSetDevice(device) != hipSuccess) return bail(nfail(err, ADE_ERR_DEVICE, "hipSetDevice failed"));
@@ -545,7 +607,38 @@ int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int
     d->inv_ws_pcm = d->d_w + o_iwp;
     d->syn_win = d->d_w + o_win;
     d->win2 = d->d_w + o_w2;
+    if (backend && reference_tables) { d->dense_fwd = d->d_w + o_df; d->dense_inv = d->d_w + o_di; }
     *out = d;
+    return ADE_OK;
+}
+
+int nkf_aec_create(const std::map<std::string, Tensor>& tensors, int in_len, int device, SubEngine** out, std::string& err) {
+    NkfAecEngine* d = nullptr;
+    const int st = nkf_build(tensors, in_len, device, false, false, &d, err);
+    *out = d;
+    return st;
+}
+
+namespace {
+struct NkfBackendImpl : NkfBackend {
+    NkfAecEngine* e = nullptr;
+    ~NkfBackendImpl() override { delete e; }
+    int frames() const override { return e->T; }
+    int reserve(int windows, std::string& err) override { return e->reserve(windows, err); }
+    int run(hipStream_t s, const int16_t* pcm, const float* fpcm, int calls, int n_win, float* wave, std::string& err) override {
+        return e->run_backend(s, pcm, fpcm, calls, n_win, wave, err);
+    }
+};
+}  // namespace
+
+int nkf_backend_create(const std::map<std::string, Tensor>& tensors, int window_len, bool reference_tables, int device, NkfBackend** out, std::string& err) {
+    *out = nullptr;
+    NkfAecEngine* d = nullptr;
+    const int st = nkf_build(tensors, window_len, device, true, reference_tables, &d, err);
+    if (st != ADE_OK) return st;
+    NkfBackendImpl* b = new NkfBackendImpl();
+    b->e = d;
+    *out = b;
     return ADE_OK;
 }
 
@@ -579,7 +672,7 @@ int NkfAecEngine::run(hipStream_t s, const int16_t* d_in, int batch, int16_t* d_
     if (st != ADE_OK) return st;
     const int ppr = (T + 1) / 2;
     hipLaunchKernelGGL(k_nkf_mean, dim3((unsigned)(batch * 2)), dim3(256), 0, s, d_in, float_in, L, mean);
-    hipLaunchKernelGGL(k_nkf_analysis, dim3((unsigned)(batch * 2 * ppr)), dim3(256), 0, s, d_in, float_in, (const float*)mean, L, T, plan, tw, win, spec);
+    hipLaunchKernelGGL(k_nkf_analysis, dim3((unsigned)(batch * 2 * ppr)), dim3(256), 0, s, d_in, float_in, (const float*)mean, L, T, plan, tw, win, spec, 1, 0);
     hipLaunchKernelGGL(k_nkf_kalman<false>, dim3((unsigned)((batch * kF + kKalmanThreads - 1) / kKalmanThreads)), dim3(kKalmanThreads), 0, s, (const float2*)spec, wts, T,
                        batch, errs, kg, (float*)nullptr);
     hipLaunchKernelGGL(k_nkf_synthesis, dim3((unsigned)(batch * ppr)), dim3(256), 0, s, (const float2*)errs, T, plan, tw, syn_win, frames_buf);
@@ -587,6 +680,31 @@ int NkfAecEngine::run(hipStream_t s, const int16_t* d_in, int batch, int16_t* d_
     hipLaunchKernelGGL(k_nkf_ola, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)frames_buf, inv_ws, inv_ws_pcm, T, keep, d_out, d_f32, total);
     NK_HIP(hipGetLastError());
     last_batch = batch;
+    return ADE_OK;
+}
+
+// The back end form: no mean kernel, the caller's [call][near, far][n_win windows] rows, every window an independent filter, a float waveform of L samples per window.
+int NkfAecEngine::run_backend(hipStream_t s, const int16_t* pcm, const float* fpcm, int calls, int n_win, float* wave, std::string& err) {
+    const int rows = calls * n_win;
+    if (rows == 0) return ADE_OK;
+    int st = reserve(rows, err);
+    if (st != ADE_OK) return st;
+    const int ppr = (T + 1) / 2;
+    if (dense_fwd)
+        gemm::launch(s, gemm::RowMajorA{dense_fwd, kN}, DenseFrameB{pcm, fpcm, L, T, n_win, 1}, DenseSpecStore{reinterpret_cast<float*>(spec)}, 2 * kF, rows * 2 * T, kN);
+    else
+        hipLaunchKernelGGL(k_nkf_analysis, dim3((unsigned)(rows * 2 * ppr)), dim3(256), 0, s, pcm, fpcm, (const float*)nullptr, L, T, plan, tw, win, spec, n_win, 1);
+    hipLaunchKernelGGL(k_nkf_kalman<false>, dim3((unsigned)((rows * kF + kKalmanThreads - 1) / kKalmanThreads)), dim3(kKalmanThreads), 0, s, (const float2*)spec, wts, T,
+                       rows, errs, kg, (float*)nullptr);
+    if (dense_inv)
+        gemm::launch(s, DenseInvA{dense_inv}, DenseErrB{reinterpret_cast<const float*>(errs)}, DenseFrameStore{frames_buf}, kN, rows * T, 2 * kF);
+    else
+        hipLaunchKernelGGL(k_nkf_synthesis, dim3((unsigned)(rows * ppr)), dim3(256), 0, s, (const float2*)errs, T, plan, tw, syn_win, frames_buf);
+    const long long total = (long long)rows * keep;
+    hipLaunchKernelGGL(k_nkf_ola, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)frames_buf, inv_ws, (const float*)nullptr, T, keep,
+                       (int16_t*)nullptr, wave, total);
+    NK_HIP(hipGetLastError());
+    last_batch = rows;
     return ADE_OK;
 }
 

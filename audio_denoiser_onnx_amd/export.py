@@ -12,6 +12,8 @@ matrices (``ERB.prepare_for_export_`` :109-114), and write the tensors under the
     python -m audio_denoiser_onnx_amd.export --family ul_unas <model_trained_on_dns3.tar> <out_dir> [--length 16000]
     python -m audio_denoiser_onnx_amd.export --family zipenhancer <pytorch_model.bin> <out_dir> [--length 32000] [--fold]
     python -m audio_denoiser_onnx_amd.export --family nkf_aec <nkf_epoch70.pt> <out_dir> [--length 32000] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
+    python -m audio_denoiser_onnx_amd.export --family dfsmn_aec <dfsmn_state.npz|.pt> <out_dir> --nkf <nkf_epoch70.pt> [--length 32000] [--no-fold] [--vad]
+                                                                                       [--in-rate 48000] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
 
 The other two families fold their checkpoints the way their export constructors do (``melband.fuse_checkpoint`` =
 Export_MelBandRoformer.py:455-538; ``mossformer.fuse_checkpoint`` = Export_MossFormer2_SS_16K.py:130-395); both folds are
@@ -199,9 +201,42 @@ def export_nkf_aec(checkpoint, out_dir, input_audio_length: int = 32000, name: s
     return model_path
 
 
+def export_dfsmn_aec(dfsmn_checkpoint, nkf_checkpoint, out_dir, input_audio_length: int = 32000, use_batch_fold: bool = True, name: str = "DFSMN_AEC",
+                     skip_connect=None, dilation=None, **meta_kw) -> Path:
+    """DFSMN-AEC (DFSMN_AEC/Export_DFSMN_AEC.py with the NKF back end) -> ``<name>.adew`` + manifest.  ``dfsmn_checkpoint``: the state dict of the ModelScope
+    ``speech_dfsmn_aec_psm_16k`` network (``linear1.linear.*``, ``deepfsmn.{i}.*``, ``linear2.*``, ``linear3.*``) with the preprocessor's ``feature.shift`` /
+    ``feature.scale``; ``nkf_checkpoint``: ``nkf_epoch70.pt``.  ``skip_connect`` / ``dilation`` (one entry per layer) are module attributes of the network, not
+    tensors: pass them, or store them in the state under ``config`` as a JSON string ``{"skip_connect": [...], "dilation": [...]}``.  The folded export with
+    1.5 s windows is the folder's default (:48-49)."""
+    import json
+    from . import dfsmn_aec
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    model_path = out_dir / f"{name}.adew"
+    sd = dict(load_state_dict(dfsmn_checkpoint)) if not isinstance(dfsmn_checkpoint, Mapping) else dict(dfsmn_checkpoint)
+    if skip_connect is None or dilation is None:
+        if "config" not in sd:
+            raise ValueError("export_dfsmn_aec: pass skip_connect and dilation, or store them in the state under 'config'")
+        cfg = json.loads(str(np.asarray(sd["config"])))
+        skip_connect, dilation = cfg["skip_connect"], cfg["dilation"]
+    nkf_sd = nkf_checkpoint if isinstance(nkf_checkpoint, Mapping) else load_state_dict(nkf_checkpoint)
+    save_blob(model_path, dfsmn_aec.state_to_blob_tensors(nkf_sd, sd, skip_connect, dilation))
+    write_metadata(model_path, dfsmn_aec.metadata(input_audio_length, use_batch_fold=use_batch_fold, name=name, **meta_kw))
+    return model_path
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     length, family, fold = None, "gtcrn", False
+    nkf_path, no_fold, vad = None, False, False
+    if "--nkf" in argv:
+        i = argv.index("--nkf")
+        nkf_path = argv[i + 1]
+        del argv[i:i + 2]
+    for flag in ("--no-fold", "--vad"):
+        if flag in argv:
+            argv.remove(flag)
+            no_fold, vad = no_fold or flag == "--no-fold", vad or flag == "--vad"
     if "--length" in argv:
         i = argv.index("--length")
         length = int(argv[i + 1])
@@ -223,7 +258,7 @@ def main(argv=None) -> int:
             i = argv.index(flag)
             gt[key] = conv(argv[i + 1])
             del argv[i:i + 2]
-    if len(argv) != 2 or family not in ("gtcrn", "h_gtcrn", "mel_band_roformer", "mossformer2_ss", "ul_unas", "zipenhancer", "nkf_aec"):
+    if len(argv) != 2 or family not in ("gtcrn", "h_gtcrn", "mel_band_roformer", "mossformer2_ss", "ul_unas", "zipenhancer", "nkf_aec", "dfsmn_aec") or (family == "dfsmn_aec" and not nkf_path):
         print(__doc__)
         return 2
     model_rate = 44100 if family == "mel_band_roformer" else 16000
@@ -242,6 +277,10 @@ def main(argv=None) -> int:
     elif family == "zipenhancer":
         path = export_zipenhancer(argv[0], argv[1], length or 32000, fold, dynamic_axes=gt["dynamic_axes"], in_sample_rate=gt["in_sample_rate"],
                                   out_sample_rate=gt["out_sample_rate"])
+    elif family == "dfsmn_aec":
+        path = export_dfsmn_aec(argv[0], nkf_path, argv[1], length or 32000, use_batch_fold=not no_fold, in_sample_rate=gt["in_sample_rate"],
+                                out_sample_rate=gt["out_sample_rate"], input_audio_dtype=gt["input_audio_dtype"], output_audio_dtype=gt["output_audio_dtype"],
+                                output_vad_result=vad)
     elif family == "nkf_aec":
         path = export_nkf_aec(argv[0], argv[1], length or 32000, out_sample_rate=gt["out_sample_rate"], input_audio_dtype=gt["input_audio_dtype"],
                               output_audio_dtype=gt["output_audio_dtype"])

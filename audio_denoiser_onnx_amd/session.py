@@ -24,6 +24,8 @@ INPUT_NAME = "noisy_audio"       # GTCRN/Export_GTCRN.py:768
 OUTPUT_NAME = "denoised_audio"   # GTCRN/Export_GTCRN.py:769
 AEC_INPUT_NAMES = ("far_end_audio", "near_end_audio")   # NKF_AEC/Export_NKF_AEC.py:524-525
 AEC_OUTPUT_NAME = "aec_audio"
+DFSMN_AEC_INPUT_NAMES = ("near_end_audio", "far_end_audio")   # DFSMN_AEC/Export_DFSMN_AEC.py:1519: the near end first
+VAD_OUTPUT_NAME = "vad_results"
 
 
 class NodeArg:
@@ -92,13 +94,20 @@ class InferenceSession:
         self.in_dtype = {"INT16": np.int16, "F32": np.float32, "F16": np.float16}[reader.string("input_audio_dtype", "INT16")]
         self.out_dtype = {"INT16": np.int16, "F32": np.float32, "F16": np.float16}[reader.string("output_audio_dtype", "INT16")]
         tname = {np.int16: "tensor(int16)", np.float32: "tensor(float)", np.float16: "tensor(float16)"}
-        self._aec = reader.string("model_family", "") == "nkf_aec"
-        if self._aec:      # two graph inputs (far end, near end), one channel each: channels 0 and 1 of the engine's planar rows (Export_NKF_AEC.py:524-525)
-            self._inputs = [NodeArg(n, [1, 1, io.in_len], tname[self.in_dtype]) for n in AEC_INPUT_NAMES]
+        family = reader.string("model_family", "")
+        self._aec = family in ("nkf_aec", "dfsmn_aec")
+        # DFSMN-AEC's optional second output: one speech probability per mask frame of every window of the call, float32 (B * windows * frames,) (:1317-1319, :1520)
+        self._vad = family == "dfsmn_aec" and bool(reader.optional_bool("output_vad_result", False))
+        if self._aec:      # two graph inputs, one channel each: channels 0 and 1 of the engine's planar rows (Export_NKF_AEC.py:524-525: far end, near end; DFSMN-AEC: near end, far end)
+            self._inputs = [NodeArg(n, [1, 1, io.in_len], tname[self.in_dtype]) for n in (DFSMN_AEC_INPUT_NAMES if family == "dfsmn_aec" else AEC_INPUT_NAMES)]
         else:
             self._inputs = [NodeArg(in_name, [1, io.in_channels, io.in_len], tname[self.in_dtype])]
         out_names = ([AEC_OUTPUT_NAME] if self._aec else [OUTPUT_NAME]) if io.n_outputs == 1 else [f"separated_{i}" for i in range(io.n_outputs)]   # Export_MossFormer2_SS_16K.py:689-690
         self._outputs = [NodeArg(name, [1, io.out_channels, io.out_len], tname[self.out_dtype]) for name in out_names]
+        if self._vad:
+            windows = reader.optional_int("export_audio_length", io.in_len) // reader.optional_int("fold_window_length", io.in_len) if reader.optional_bool("use_batch_fold", False) else 1
+            self.vad_frames = windows * io.frames                # per batch item
+            self._outputs.append(NodeArg(VAD_OUTPUT_NAME, [self.vad_frames], "tensor(float)"))
         self._planar_name = "far_end_near_end_audio"            # (internal: the interleaved two-input tensor of an AEC call)
         self._inputs_meta, self._outputs_meta = self._inputs, self._outputs   # names the reference script touches
         validate_audio_metadata(reader, self)
@@ -118,7 +127,15 @@ class InferenceSession:
 
     def run(self, output_names, input_feed: Dict[str, np.ndarray], return_f32: bool = False):
         """``session.run(None, {"noisy_audio": int16 (B,1,L)})`` -> ``[int16 (B,1,L_out)]`` (+ fp32 pre-PCM tap).
-        NKF-AEC: ``{"far_end_audio": (B,1,L), "near_end_audio": (B,1,L)}`` -> ``[aec_audio (B,1,L_out)]``."""
+        NKF-AEC: ``{"far_end_audio": (B,1,L), "near_end_audio": (B,1,L)}`` -> ``[aec_audio (B,1,L_out)]``.
+        DFSMN-AEC: ``{"near_end_audio": ..., "far_end_audio": ...}`` -> ``[aec_audio]``, and with ``output_vad_result`` a last element ``vad_results`` float32 (B * frames,)."""
+        out = self._run_audio(input_feed, return_f32)
+        if self._vad:
+            batch = int(np.asarray(input_feed[self._inputs[0].name]).shape[0])
+            out.append(self.tap(VAD_OUTPUT_NAME, batch * self.vad_frames).copy())
+        return out
+
+    def _run_audio(self, input_feed: Dict[str, np.ndarray], return_f32: bool = False):
         if self._aec:
             parts = []
             for arg in self._inputs:
@@ -130,7 +147,7 @@ class InferenceSession:
                 parts.append(a)
             if parts[0].shape[0] != parts[1].shape[0] or parts[0].dtype != parts[1].dtype:
                 raise ValueError("far_end_audio and near_end_audio must have the same batch size and dtype")
-            input_feed = {self._planar_name: np.concatenate(parts, axis=1)}      # planar (B, 2, L): far end, near end
+            input_feed = {self._planar_name: np.concatenate(parts, axis=1)}      # planar (B, 2, L), in the order of the graph inputs
         name = self._planar_name if self._aec else self._inputs[0].name
         if name not in input_feed:
             raise KeyError(f"missing input {name!r}")

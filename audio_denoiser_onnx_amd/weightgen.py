@@ -55,3 +55,45 @@ def materialise(spec: Iterable[Tuple[str, Sequence[int], float]], seed: int = 0)
 # fc_out_dense2 (weight and bias) multiplied by this factor.  The per-bin Kalman recurrence is only stable with a small gain: default init, or more than
 # about 0.03 x default on that layer, diverges (NaN or a 10 x output RMS), and fp32 evaluations of a diverging filter disagree by tens of LSB.
 NKF_GAIN_LAYER_SCALE = 1e-2
+
+
+def dfsmn_aec_state(seed: int = 0, width: int = 128, hidden: int = 64, depth: int = 6, lorder: int = 20, dilation: int = 2):
+    """Seeded DFSMN-AEC weights for benchmarks and smoke runs: ``(nkf_state, dfsmn_state, skip_connect, dilation)``, the arguments of
+    ``dfsmn_aec.state_to_blob_tensors``.  The NKF half is uniform in +- 1 / sqrt(fan_in) (PyTorch's default range) with the Kalman-gain layer scaled by
+    NKF_GAIN_LAYER_SCALE (the stability rule above); the DFSMN half has the attribute paths of the ModelScope network, scaled so that activations stay of order
+    one, and a feature shift / scale that centres int16-scale log-mel energies."""
+    L, fc, rnn, feat, bins = 4, 18, 18, 240, 321
+    nkf = {}
+
+    def put(dst, name, shape, fan_in, gain=1.0):
+        dst[name] = tensor(name, shape, gain / np.sqrt(fan_in), seed)
+
+    for part in ("real", "imag"):
+        put(nkf, f"kg_net.fc_in.0.linear_{part}.weight", (fc, 2 * L + 1), 2 * L + 1)
+        put(nkf, f"kg_net.fc_in.0.linear_{part}.bias", (fc,), 2 * L + 1)
+        put(nkf, f"kg_net.fc_out.0.linear_{part}.weight", (fc, rnn), rnn)
+        put(nkf, f"kg_net.fc_out.0.linear_{part}.bias", (fc,), rnn)
+        put(nkf, f"kg_net.fc_out.2.linear_{part}.weight", (L, fc), fc, NKF_GAIN_LAYER_SCALE)
+        put(nkf, f"kg_net.fc_out.2.linear_{part}.bias", (L,), fc, NKF_GAIN_LAYER_SCALE)
+    for g in ("gru_r", "gru_i"):
+        put(nkf, f"kg_net.complex_gru.{g}.weight_ih_l0", (3 * rnn, fc), rnn)
+        put(nkf, f"kg_net.complex_gru.{g}.weight_hh_l0", (3 * rnn, rnn), rnn)
+        put(nkf, f"kg_net.complex_gru.{g}.bias_ih_l0", (3 * rnn,), rnn)
+        put(nkf, f"kg_net.complex_gru.{g}.bias_hh_l0", (3 * rnn,), rnn)
+    nkf["kg_net.fc_in.1.prelu.weight"] = np.full((1,), 0.25, np.float32)
+    nkf["kg_net.fc_out.1.prelu.weight"] = np.full((1,), 0.25, np.float32)
+    net = {}
+    put(net, "linear1.linear.weight", (width, feat), feat, 1.0)
+    put(net, "linear1.linear.bias", (width,), 100.0)
+    for i in range(depth):
+        put(net, f"deepfsmn.{i}.linear.weight", (hidden, width), width, 2.0)
+        put(net, f"deepfsmn.{i}.linear.bias", (hidden,), 100.0)
+        put(net, f"deepfsmn.{i}.project.weight", (width, hidden), hidden, 1.2)
+        put(net, f"deepfsmn.{i}.conv1.weight", (width, 1, lorder, 1), 50.0)
+    put(net, "linear2.weight", (bins, width), width, 0.9)
+    put(net, "linear2.bias", (bins,), 100.0)
+    put(net, "linear3.weight", (1, width), width, 0.9)
+    put(net, "linear3.bias", (1,), 100.0)
+    net["feature.shift"] = np.full((feat,), -15.0, np.float32)
+    net["feature.scale"] = np.full((feat,), 0.2, np.float32)
+    return nkf, net, [i % 2 == 0 for i in range(depth)], [dilation] * depth
