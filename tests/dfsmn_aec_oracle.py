@@ -108,7 +108,7 @@ class DfsmnAecOracle:
 
     def forward(self, near, far, fold_window=0, int_in=True, int_out=True):
         """near, far: (B, L) int16 (or normalised floats with int_in=False) -> (output (B, L) int16 / float32, dict of taps).
-        Taps (rows = B * windows): temp_aec (rows, W), feat (rows, Tm, 240), mask (rows, Tm, 321), vad_results (rows * Tm), wave (B, L)."""
+        Taps (rows = B * windows): temp_aec (rows, W), spec complex (rows, Tm, 321), feat (rows, Tm, 240), mask (rows, Tm, 321), vad_results (rows * Tm), wave (B, L)."""
         near, far = np.asarray(near, np.float64), np.asarray(far, np.float64)
         if int_in:
             near, far = near / 32768.0, far / 32768.0
@@ -134,7 +134,7 @@ class DfsmnAecOracle:
         mask, vad = self.network(feat)
         wave = _istft(spec_a * mask, wa, ca, sa, HA, 0, W).reshape(B, L)
         out = np.trunc(np.clip(wave * 32767.0, -32768, 32767)).astype(np.int16) if int_out else wave.astype(np.float32)
-        return out, {"temp_aec": temp, "feat": feat, "mask": mask, "vad_results": vad.reshape(-1), "wave": wave}
+        return out, {"temp_aec": temp, "spec": spec_a, "feat": feat, "mask": mask, "vad_results": vad.reshape(-1), "wave": wave}
 
 
 def load_blob_tensors(path):

@@ -3,7 +3,8 @@
 tests/hipsim/build.sh compiles a fixed source list without csrc/ade_nkf_aec.hip and csrc/ade_dfsmn_aec.hip (its library answers ADE_ERR_UNSUPPORTED for the
 family: the weak dfsmn_aec_create).  This test builds its OWN simulator library with the same g++ line plus those two files, into a separate file, and runs a
 short unfolded case and a two-window folded case with the default tables (the back end's dense reference-table products) and the unfolded case again with
-ade_dft_tables = exact (its FFT kernels).  The oracle runs with the matching tables.
+ade_dft_tables = exact (its FFT kernels).  The oracle runs with the matching tables.  feat, mask and vad_results are held to the seed-0 gates of
+tests/test_dfsmn_aec_gpu.py for the matching table mode (read from dfsmn_aec_seed0_taps.npz).
 """
 import os
 import subprocess
@@ -28,8 +29,8 @@ LIB = os.path.join(HERE, "hipsim", "_build", "libade_hipsim_dfsmn_aec.so")
 GOLD = os.path.join(HERE, "golden")
 
 
-@pytest.fixture(scope="module")
-def simlib():
+def build_simlib():
+    """The simulator library with the two AEC engines, built once (tests/test_aec_geometry.py loads the same file)."""
     import glob
     from audio_denoiser_onnx_amd import _lib
     deps = [os.path.join(CSRC, s) for s in SOURCES] + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "hipsim", "hipsim.cpp"),
@@ -40,6 +41,19 @@ def simlib():
                         os.path.join(HERE, "hipsim"), "-x", "c++"] + [os.path.join(CSRC, s) for s in SOURCES] +
                        ["-x", "c++", os.path.join(HERE, "hipsim", "hipsim.cpp"), "-o", LIB], check=True, cwd=REPO)
     return _lib.AdeLibrary(LIB)
+
+
+@pytest.fixture(scope="module")
+def simlib():
+    return build_simlib()
+
+
+def _gates(dft_tables):
+    """The seed-0 gates of tests/test_dfsmn_aec_gpu.py, read from the fixture's recorded distances for the matching table mode."""
+    import json
+    from aec_geometry_lib import gate
+    dist = json.loads(str(np.load(os.path.join(GOLD, "dfsmn_aec_seed0_taps.npz"))["fp64_distance"]))["engine" if dft_tables == "reference" else "exact"]
+    return {k: gate(dist, k) for k in ("feat", "mask", "vad_results")}
 
 
 def _check(simlib, length, fold, window_seconds, rows, dft_tables="reference"):
@@ -70,6 +84,9 @@ def _check(simlib, length, fold, window_seconds, rows, dft_tables="reference"):
     print(f"hipsim vs oracle: temp_aec {d_temp:.2e} feat {d_feat:.2e} mask {d_mask:.2e} vad {d_vad:.2e} wave {d_wave:.2e} pcm {lsb} LSB")
     assert vad.shape == (taps["vad_results"].size,)
     assert d_wave <= 1e-4 and lsb <= 1 and d_temp <= 1e-4
+    g = _gates(dft_tables)
+    print("gates:", " ".join(f"{k} {v:.3e}" for k, v in g.items()))
+    assert d_feat <= g["feat"] and d_mask <= g["mask"] and d_vad <= g["vad_results"], (d_feat, d_mask, d_vad, g)
     return sess
 
 

@@ -15,6 +15,8 @@ What stands in for the parts the container lacks:
     ``weightgen.NKF_GAIN_LAYER_SCALE`` (the stability rule of tools/make_golden_nkf_aec.py).
 
     python tools/make_golden_dfsmn_aec.py      # writes tests/golden/dfsmn_aec_seed0.adew and dfsmn_aec_seed0_*.npz
+    python tools/make_golden_dfsmn_aec.py --geometry      # writes tests/golden/aec_geom_<name>.npz only: the geometries of tests/aec_geometry_lib.py, whose
+                                                          # generated weights (per-layer H / lorder / dilation / skip, distinct PReLU slopes) replace the stand-ins
 """
 import ast
 import json
@@ -37,7 +39,7 @@ from audio_denoiser_onnx_amd import dfsmn_aec, kaldi_mel  # noqa: E402
 from audio_denoiser_onnx_amd import weights as W  # noqa: E402
 from audio_denoiser_onnx_amd.wavio import read_pcm16  # noqa: E402
 from audio_denoiser_onnx_amd.weightgen import NKF_GAIN_LAYER_SCALE  # noqa: E402
-from make_golden_nkf_aec import checkpoint_names  # noqa: E402
+from make_golden_nkf_aec import checkpoint_names, load_checkpoint  # noqa: E402
 
 GOLD = os.path.join(REPO, "tests", "golden")
 L = 32000
@@ -57,6 +59,11 @@ def import_namespace(**over) -> dict:
             break                                                            # print('Export start ...'): everything from here on is the export itself
         if isinstance(node, (ast.ClassDef, ast.FunctionDef, ast.If)):
             keep.append(node)
+            # An ``if`` block may re-derive an overridden setting: for the NKF back end the export sets ``INPUT_AUDIO_LENGTH = max(32000, ...)`` (:87), a
+            # recommendation and not a limit of the model.  Such a name is assigned its override again right after the block.
+            if isinstance(node, ast.If):
+                inner = {t.id for a in ast.walk(node) if isinstance(a, ast.Assign) for t in a.targets if isinstance(t, ast.Name)}
+                keep.extend(ast.parse(f"{n} = {over[n]!r}").body[0] for n in sorted(inner & set(over)))
         elif isinstance(node, ast.Assign):
             names = [t.id for t in node.targets if isinstance(t, ast.Name)]
             if names and (all(n.upper() == n and not n.startswith("_") for n in names) or names == ["project_path_B"]):
@@ -116,8 +123,50 @@ def fake_dfsmn(seed: int):
     return pipe, state
 
 
-def build(ns, seed=0, double=False):
-    """The construction of Export_DFSMN_AEC.py:1394-1505 for the NKF back end."""
+def dfsmn_from_state(state, skip_connect, dilation):
+    """The stand-in tree of fake_dfsmn with every dimension and weight taken from a state dict (tests/aec_geometry_lib.state): per-layer hidden size, lorder,
+    dilation and skip_connect.  The reference pads every layer by layer 0's ``padding_left``, so ``dilation * (lorder - 1)`` must be one number."""
+    t = {k: torch.from_numpy(np.asarray(v, np.float32).copy()) for k, v in state.items()}
+    width = t["linear1.linear.weight"].shape[0]
+
+    def lin(key, bias=True):
+        o, i = t[key + ".weight"].shape
+        m = nn.Linear(i, o, bias=bias)
+        with torch.no_grad():
+            m.weight.copy_(t[key + ".weight"])
+            if bias:
+                m.bias.copy_(t[key + ".bias"])
+        return m
+
+    class Layer(nn.Module):
+        def __init__(self, i):
+            super().__init__()
+            lorder = t[f"deepfsmn.{i}.conv1.weight"].shape[2]
+            self.linear, self.act, self.norm, self.project = lin(f"deepfsmn.{i}.linear"), nn.ReLU(), nn.Identity(), lin(f"deepfsmn.{i}.project", bias=False)
+            self.conv1 = nn.Conv2d(width, width, (lorder, 1), dilation=(dilation[i], 1), groups=width, bias=False)
+            with torch.no_grad():
+                self.conv1.weight.copy_(t[f"deepfsmn.{i}.conv1.weight"])
+            self.skip_connect, self.output_dim, self.padding_left = bool(skip_connect[i]), width, dilation[i] * (lorder - 1)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.linear1 = nn.Module()
+            self.linear1.linear = lin("linear1.linear")
+            self.relu, self.sig = nn.ReLU(), nn.Sigmoid()
+            self.deepfsmn = nn.ModuleList([Layer(i) for i in range(len(skip_connect))])
+            self.linear2, self.linear3 = lin("linear2"), lin("linear3")
+
+    net = Net().eval()
+    assert len({l.padding_left for l in net.deepfsmn}) == 1, "the reference shares layer 0's left pad"
+    got = {k: v.numpy() for k, v in net.state_dict().items()}
+    assert set(got) == set(state) - {"feature.shift", "feature.scale"} and all(np.array_equal(got[k], state[k]) for k in got)
+    return types.SimpleNamespace(model=net, preprocessor=types.SimpleNamespace(feature=types.SimpleNamespace(shift=t["feature.shift"], scale=t["feature.scale"])))
+
+
+def build(ns, seed=0, double=False, geometry=None):
+    """The construction of Export_DFSMN_AEC.py:1394-1505 for the NKF back end.  ``geometry``: ``(nkf_state, dfsmn_state, skip_connect, dilation)`` of
+    tests/aec_geometry_lib.state, loaded in place of the seeded stand-ins."""
     S = ns["STFT_Process"]
     static = ns["STATIC_EXPORT"]
     assert static
@@ -134,13 +183,16 @@ def build(ns, seed=0, double=False):
     torch.manual_seed(seed)
     nkf = ns["NKF_Inner"](L=ns["FILTER_ORDER"], fc_dim=ns["FC_DIM"], rnn_layers=ns["RNN_LAYERS"], rnn_dim=ns["RNN_DIM"], custom_stft=stft_b, custom_istft=istft_b,
                           max_frames=ns["BACKEND_FRAMES_B"], model_batch=ns["MODEL_BATCH"]).eval()
-    with torch.no_grad():
-        for p in nkf.kg_net.fc_out_dense2.parameters():
-            p.mul_(NKF_GAIN_LAYER_SCALE)
+    if geometry is not None:
+        load_checkpoint(nkf, geometry[0])
+    else:
+        with torch.no_grad():
+            for p in nkf.kg_net.fc_out_dense2.parameters():
+                p.mul_(NKF_GAIN_LAYER_SCALE)
     nkf_state = checkpoint_names({k: v.detach().clone().numpy() for k, v in nkf.state_dict().items() if k.startswith("kg_net.") and "buffer" not in k})
     nkf = nkf.float().eval()
     nkf.cache_export_constants_()
-    pipe, dfsmn_state = fake_dfsmn(seed)
+    pipe, dfsmn_state = (dfsmn_from_state(*geometry[1:]), geometry[1]) if geometry is not None else fake_dfsmn(seed)
     model = ns["DFSMN_AEC"](pipe, light_aec=nkf, light_aec_type="NKF", custom_stft_A2=stft_a2, custom_istft_A2=istft_a2, custom_stft_B=None, nfft_A=ns["NFFT_A"],
                             win_length_A=ns["WINDOW_LENGTH_A"], hop_length_A=ns["HOP_LENGTH_A"], pre_emphasis=ns["PRE_EMPHASIZE"],
                             in_sample_rate=ns["IN_SAMPLE_RATE"], out_sample_rate=ns["OUT_SAMPLE_RATE"], n_mels=ns["N_MELS"], use_batch_fold=ns["USE_BATCH_FOLD"],
@@ -155,7 +207,7 @@ def run(ns, model, near, far, dtype=torch.int16, taps=False):
     """-> (audio flat, vad or None, taps dict)"""
     got = {}
     F = ns["torch"].nn.functional
-    orig_linear, nkf_fwd, istft_fwd = F.linear, model.light_aec.forward, model.custom_istft_A2.forward
+    orig_linear, nkf_fwd, istft_fwd, stft_fwd = F.linear, model.light_aec.forward, model.custom_istft_A2.forward, model.custom_stft_A2.forward
 
     def linear_spy(x, w, b=None):
         if w is model.feature_linear_weight:
@@ -172,8 +224,12 @@ def run(ns, model, near, far, dtype=torch.int16, taps=False):
         y = istft_fwd(x)
         got["wave"] = y.detach().clone().numpy()
         return y
+    def stft_spy(x):
+        y = stft_fwd(x)
+        got["spec"] = y.detach().clone().numpy()                    # (rows, [re 321 | im 321], Tm)
+        return y
     if taps:
-        F.linear, model.light_aec.forward, model.custom_istft_A2.forward = linear_spy, nkf_spy, istft_spy
+        F.linear, model.light_aec.forward, model.custom_istft_A2.forward, model.custom_stft_A2.forward = linear_spy, nkf_spy, istft_spy, stft_spy
         sig = model.dfsmn_aec.sig.forward
         masks = []
         model.dfsmn_aec.sig.forward = lambda x: masks.append(sig(x)) or masks[-1]
@@ -182,7 +238,7 @@ def run(ns, model, near, far, dtype=torch.int16, taps=False):
             y = model(torch.from_numpy(np.ascontiguousarray(near)).reshape(1, 1, -1).to(dtype), torch.from_numpy(np.ascontiguousarray(far)).reshape(1, 1, -1).to(dtype))
     finally:
         if taps:
-            F.linear, model.light_aec.forward, model.custom_istft_A2.forward = orig_linear, nkf_fwd, istft_fwd
+            F.linear, model.light_aec.forward, model.custom_istft_A2.forward, model.custom_stft_A2.forward = orig_linear, nkf_fwd, istft_fwd, stft_fwd
             model.dfsmn_aec.sig.forward = sig
     vad = None
     if isinstance(y, tuple):
@@ -359,5 +415,99 @@ def main(seed=0):
             print(fn_, os.path.getsize(os.path.join(GOLD, fn_)))
 
 
+def geometry_fixtures():
+    """tests/golden/aec_geom_<name>.npz for every geometry of tests/aec_geometry_lib.py: the reference's DFSMN_AEC.forward (unfolded 3200, every row; folded
+    2 x 1600, two calls) and NKF.forward (3200 and 3000 samples) on the generated weights, and the recorded distances the tests' gates are read from."""
+    import hashlib
+    import aec_geometry_lib as G
+    import make_golden_nkf_aec as nkf_tool
+    from dfsmn_aec_oracle import DfsmnAecOracle
+    from nkf_aec_oracle import NkfAecOracle
+    WL, WF = G.W_LONG, G.W_FOLD
+    ns = import_namespace(USE_BATCH_FOLD=False, INPUT_AUDIO_LENGTH=WL, OUTPUT_VAD_RESULT=True)
+    ns_f = import_namespace(USE_BATCH_FOLD=True, INPUT_AUDIO_LENGTH=WL, BATCH_WINDOW_SECONDS=G.FOLD_SECONDS, OUTPUT_VAD_RESULT=True)
+    Tm, Tf = dfsmn_aec.mask_frames(WL), dfsmn_aec.mask_frames(WF)
+    assert ns["MODEL_BATCH"] == 1 and ns["MASK_FRAMES_A2"] == Tm == 9 and ns["BACKEND_FRAMES_B"] == 13
+    assert ns_f["FOLD_WINDOW_LENGTH"] == WF and ns_f["EXPORT_AUDIO_LENGTH"] == WL and ns_f["MODEL_BATCH"] == 2 and ns_f["MASK_FRAMES_A2"] == Tf == 4
+    ns_n = {L: nkf_tool.import_namespace(L) for L in G.NKF_LENGTHS}
+    for name in G.GEOMETRIES:
+        geometry = G.state(name)
+        blob = dfsmn_aec.state_to_blob_tensors(*geometry)
+        model, _, _ = build(ns, geometry=geometry)
+        for k in ("feature_linear_weight", "feature_linear_bias"):          # the folded first layer is the reference's own buffer, bit for bit
+            assert np.array_equal(blob[k], getattr(model, k).numpy()), k
+        near, far = G.signals(name)
+        fix = {"near": near, "far": far, "blob_sha256": np.asarray(hashlib.sha256(W.pack_blob(blob)).hexdigest())}
+        outs, vads, row_taps = [], [], []
+        for i in range(G.N_ROWS):
+            pcm, vad, taps = run(ns, model, near[i], far[i], taps=True)
+            outs.append(pcm.astype(np.int16))
+            vads.append(vad.astype(np.float32))
+            sp = taps["spec"].reshape(2, dfsmn_aec.N_BINS, Tm)
+            row_taps.append({"temp_aec": taps["temp_aec"].reshape(-1), "spec": np.stack([sp[0].T, sp[1].T], axis=-1),
+                             "feat": taps["feat"].reshape(Tm, dfsmn_aec.FEAT_DIM), "mask": taps["mask"].reshape(Tm, dfsmn_aec.N_BINS), "vad_results": vads[i],
+                             "wave": taps["wave"].reshape(-1)})
+        assert outs[0].any() and outs[1].any() and outs[3].any() and not outs[2].any(), "live rows, and all-zero input must give all-zero PCM"
+        fix["out"], fix["vad"] = np.stack(outs), np.stack(vads)
+        tap_fix = row_taps[0]
+        for k, v in tap_fix.items():
+            fix["tap_" + k] = np.ascontiguousarray(v, np.float32)
+        model_f, _, _ = build(ns_f, geometry=geometry)
+        folded = [run(ns_f, model_f, near[i], far[i]) for i in (0, 3)]
+        fix["fold_out"], fix["fold_vad"] = np.stack([f[0].astype(np.int16) for f in folded]), np.stack([f[1].astype(np.float32) for f in folded])
+        # the distance between the reference's fp32 run and the float64 oracle per tap, as dfsmn_aec_seed0_taps.npz records it (see main): row 0, which the
+        # gates are read from.  ``<tap>_all_rows`` is the same distance over every row of the long shape (far end silent and all zero included): a record that
+        # the reference's own fp32 run is no further from the oracle on the rows whose taps are not kept than on row 0
+        dist = {}
+        for tables in ("reference", "exact", "engine"):
+            oracle = DfsmnAecOracle(blob, tables="reference", mask_tables="exact") if tables == "engine" else DfsmnAecOracle(blob, tables=tables)
+            opcm, otaps = oracle.forward(near[:1], far[:1])
+            otaps["spec"] = np.stack([otaps["spec"].real, otaps["spec"].imag], axis=-1)
+            d = {}
+            for k in tap_fix:
+                ref = tap_fix[k].astype(np.float32).astype(np.float64).reshape(-1)
+                d[k] = float(np.abs(otaps[k].reshape(-1) - ref).max())
+                d[k + "_peak"] = float(np.abs(ref).max())
+            d["pcm_lsb"] = int(np.abs(opcm[0].astype(np.int32) - outs[0].astype(np.int32)).max())
+            _, otaps_all = oracle.forward(near, far)
+            otaps_all["spec"] = np.stack([otaps_all["spec"].real, otaps_all["spec"].imag], axis=-1)
+            for k in tap_fix:
+                ref = np.stack([r[k] for r in row_taps]).astype(np.float32).astype(np.float64).reshape(-1)
+                d[k + "_all_rows"] = float(np.abs(otaps_all[k].reshape(-1) - ref).max())
+            opcm_f, _ = oracle.forward(near[[0, 3]], far[[0, 3]], fold_window=WF)
+            d["fold_pcm_lsb"] = int(np.abs(opcm_f.astype(np.int32) - fix["fold_out"].astype(np.int32)).max())
+            dist[tables] = d
+            print(f"{name}: fp32 reference vs float64 oracle ({tables} tables): " + ", ".join(f"{k} {v:.3e}" if isinstance(v, float) else f"{k} {v}" for k, v in d.items()))
+        fix["fp64_distance"] = np.asarray(json.dumps(dist))
+        # NKF.forward on the same NKF weights: rows 0, 1 (far end silent) and 3.  The engine's transforms are FFTs, so its oracle has exact tables; the recorded
+        # distance of echo_hat and kg is the one between the reference-table and the exact-table oracle (the two things the existing fixtures set side by side)
+        nkf_dist = {}
+        for L in G.NKF_LENGTHS:
+            model_n, _ = nkf_tool.build(ns_n[L], state=geometry[0])
+            rows_n = (0, 1, 3)
+            ref_runs = [nkf_tool.run(model_n, np.ascontiguousarray(far[i, :L]), np.ascontiguousarray(near[i, :L])) for i in rows_n]
+            keep = ref_runs[0][0].size
+            assert keep == 256 * (L // 256) and not np.any(ref_runs[1][2]), "far end zero must give echo_hat == 0"
+            fix[f"nkf_out_{L}"] = np.stack([r[0].astype(np.int16) for r in ref_runs])
+            ex = NkfAecOracle(blob, tables="exact").forward(far[rows_n, :L], near[rows_n, :L], want_taps=True, audio_len=keep)
+            rf = NkfAecOracle(blob, tables="reference").forward(far[rows_n, :L], near[rows_n, :L], want_taps=True, audio_len=keep)
+            ref_wave = np.stack([r[1][:keep].astype(np.float64) / 32767.0 for r in ref_runs])
+            ref_echo = np.stack([r[2][0, 0] + 1j * r[2][1, 0] for r in ref_runs])                      # (rows, F, T)
+            d = {"echo_hat": float(np.abs(ex[2]["echo_hat"] - rf[2]["echo_hat"]).max()), "echo_hat_peak": float(np.abs(ex[2]["echo_hat"]).max()),
+                 "kg": float(np.abs(ex[2]["kg"] - rf[2]["kg"]).max()), "kg_peak": float(np.abs(ex[2]["kg"]).max()),
+                 "wave": float(np.abs(ex[1] - ref_wave).max()), "wave_peak": float(np.abs(ref_wave).max()),
+                 "echo_hat_fp32": float(np.abs(ex[2]["echo_hat"] - ref_echo).max()),
+                 "pcm_lsb": int(np.abs(ex[0].astype(np.int32) - fix[f"nkf_out_{L}"].astype(np.int32)).max())}
+            nkf_dist[str(L)] = d
+            print(f"{name}: NKF {L}: " + ", ".join(f"{k} {v:.3e}" if isinstance(v, float) else f"{k} {v}" for k, v in d.items()))
+        fix["nkf_distance"] = np.asarray(json.dumps(nkf_dist))
+        path = os.path.join(GOLD, f"aec_geom_{name}.npz")
+        np.savez_compressed(path, **fix)
+        print(os.path.basename(path), os.path.getsize(path))
+
+
 if __name__ == "__main__":
-    main()
+    if "--geometry" in sys.argv:
+        geometry_fixtures()
+    else:
+        main()

@@ -62,7 +62,8 @@ def import_namespace(length: int, in_dtype: str = "INT16", out_dtype: str = "INT
     return ns
 
 
-def build(ns, seed=0):
+def build(ns, seed=0, state=None):
+    """``state``: a checkpoint-named NKF state dict to load instead of the seeded initialisation (the geometry fixtures' generated weights)."""
     STFT_Process = ns["STFT_Process"]
     int_in, int_out = "int" in ns["IN_AUDIO_DTYPE"].lower(), "int" in ns["OUT_AUDIO_DTYPE"].lower()
     stft = STFT_Process(model_type="stft_B", n_fft=ns["NFFT"], hop_len=ns["HOP_LENGTH"], win_length=ns["WINDOW_LENGTH"], max_frames=0,
@@ -74,9 +75,12 @@ def build(ns, seed=0):
     model = ns["NKF"](L=ns["FILTER_ORDER"], fc_dim=ns["FC_DIM"], rnn_layers=ns["RNN_LAYERS"], rnn_dim=ns["RNN_DIM"], custom_stft=stft, custom_istft=istft,
                       max_frames=ns["MAX_SIGNAL_LENGTH"], in_sample_rate=ns["IN_SAMPLE_RATE"], out_sample_rate=ns["OUT_SAMPLE_RATE"],
                       use_batch_fold=ns["USE_BATCH_FOLD"], fold_window=ns["FOLD_WINDOW_LENGTH"]).eval()
-    with torch.no_grad():
-        for p in model.kg_net.fc_out_dense2.parameters():
-            p.mul_(NKF_GAIN_LAYER_SCALE)
+    if state is not None:
+        load_checkpoint(model, state)
+    else:
+        with torch.no_grad():
+            for p in model.kg_net.fc_out_dense2.parameters():
+                p.mul_(NKF_GAIN_LAYER_SCALE)
     state = {k: v.detach().clone().numpy() for k, v in model.state_dict().items() if k.startswith("kg_net.")}
     model.cache_export_constants_()                                                                    # (:509)
     return model, state
@@ -91,6 +95,22 @@ def checkpoint_names(state):
         parts[1] = ren.get(parts[1], parts[1])
         out[".".join(parts)] = v
     return out
+
+
+def load_checkpoint(model, state):
+    """checkpoint-named weights -> the export module, every ``kg_net.`` parameter (what load_nkf_weights does, Export_NKF_AEC.py:414-455)"""
+    ren = {"fc_in.0": "fc_in_dense", "fc_in.1": "fc_in_act", "fc_out.0": "fc_out_dense1", "fc_out.1": "fc_out_act", "fc_out.2": "fc_out_dense2"}
+    own = {k: v for k, v in model.state_dict().items() if k.startswith("kg_net.") and "buffer" not in k}
+    new = {}
+    for k, v in state.items():
+        parts = k.split(".")
+        two = ".".join(parts[1:3])
+        parts = [parts[0], ren[two]] + parts[3:] if two in ren else parts
+        new[".".join(parts)] = torch.from_numpy(np.asarray(v, np.float32).copy())
+    assert set(new) == set(own), sorted(set(new) ^ set(own))
+    model.load_state_dict(new, strict=False)
+    for k, v in new.items():
+        assert torch.equal(model.state_dict()[k], v.reshape(model.state_dict()[k].shape)), k
 
 
 def run(model, far, near, dtype=torch.int16):
