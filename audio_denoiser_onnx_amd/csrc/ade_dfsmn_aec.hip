@@ -17,6 +17,16 @@
 //   k_dfa_synthesis   mask * spectrum -> Hermitian inverse 640-point FFT (two frames per transform) -> * symmetric hamming / 640
 //   k_dfa_ola         overlap-add at hop 320 as a gather (at most two frames per sample), * 1 / window-square sum -> the f32 waveform; * 32767, clamp, truncate -> int16
 // Every network dimension (width, hidden sizes, lorder, dilation, depth) is read from the blob.
+//
+// Streams (ade_stream_* on a dfsmn_aec handle, include/ade.h; DESIGN.md section 11, "Streaming"): a push of F hops continues the signal, 1344 samples behind the input --
+//   back end             NkfBackend::stream_step: the stream kernels of csrc/ade_nkf_aec.hip, the float temp_aec of the step left in device memory
+//   k_dfa_stream_stage   the push's near-end samples and the step's temp_aec samples into two rings addressed by the signal's sample index
+//   k_dfa_features       the same kernel, its 640 samples per frame read from the rings (RingSrc)
+//   mask network         the same GEMMs, N = streams x the frames the push completes
+//   k_dfa_stream_memory  the memory with the frames before the push taken from the layer's history, which it also renews
+//   k_dfa_stream_synthesis  ONE frame per transform (a pair would make a frame's bits depend on where the push ends)
+//   k_dfa_stream_out     overlap-add gather, the one-shot's 1 / window-square table, the samples that are final but not yet due, the PCM tail
+// Every count is a function of the hops pushed and is computed on the host.
 #include "ade_fft.h"
 #include "ade_gemm.h"
 #include "ade_internal.h"
@@ -54,9 +64,38 @@ struct MaskTStore {            // mask[j][f] = sigmoid(v + bias[f]): linear2, st
     __device__ void operator()(int f, int j, float v, float b, gemm::None, gemm::None) const { out[(size_t)j * kFA + f] = 1.0f / (1.0f + expf(-(v + b))); }
 };
 
-// Frame fr = row * Tm + t of window row = call * n_win + w: the near end is channel 0 of the caller's [call][2][n_win * W] rows, temp_aec is [row][W].
-__global__ __launch_bounds__(256) void k_dfa_features(const int16_t* __restrict__ pcm, const float* __restrict__ fpcm, const float* __restrict__ temp, int W, int Tm, int n_win,
-                                                      int nframes, fft::Plan p1024, fft::Plan p640, const float2* __restrict__ tw1024, const float2* __restrict__ tw640,
+// Where k_dfa_features takes the 640 (near, temp_aec) samples of mask frame fr from.
+// One-shot: frame fr = row * Tm + t of window row = call * n_win + w: the near end is channel 0 of the caller's [call][2][n_win * W] rows, temp_aec is [row][W].
+struct CallSrc {
+    const int16_t* pcm;
+    const float* fpcm;
+    const float* temp;
+    int W, Tm, n_win;
+    struct Frame { const int16_t* pcm; const float* fpcm; const float* temp; size_t at_near, at_temp; };
+    __device__ Frame frame(int fr) const {
+        const int row = fr / Tm, t = fr - row * Tm, call = row / n_win, w = row - call * n_win;
+        return Frame{pcm, fpcm, temp, ((size_t)call * 2 * n_win + w) * W + (size_t)t * kHA, (size_t)row * W + (size_t)t * kHA};
+    }
+    static __device__ float near(const Frame& f, int n) { return (f.fpcm ? f.fpcm[f.at_near + n] : (float)f.pcm[f.at_near + n]) * (1.0f / 32768.0f); }
+    static __device__ float temp_aec(const Frame& f, int n) { return f.temp[f.at_temp + n]; }
+};
+// Streams: frame fr = stream * Mp + i is the i-th frame the push completes; sample n of it sits in the stream's rings at (offset of the push's first frame + 320 i + n)
+// modulo the ring length (the rings are addressed by the signal's sample index; the offsets come from the host).
+struct RingSrc {
+    const int16_t* near_ring;
+    const float* temp_ring;
+    int Mp, RN, RT, near_off, temp_off;
+    struct Frame { const int16_t* nr; const float* tr; int RN, RT, n0, t0; };
+    __device__ Frame frame(int fr) const {
+        const int st = fr / Mp, i = fr - st * Mp;
+        return Frame{near_ring + (size_t)st * RN, temp_ring + (size_t)st * RT, RN, RT, (near_off + i * kHA) % RN, (temp_off + i * kHA) % RT};
+    }
+    static __device__ float near(const Frame& f, int n) { int p = f.n0 + n; if (p >= f.RN) p -= f.RN; return (float)f.nr[p] * (1.0f / 32768.0f); }
+    static __device__ float temp_aec(const Frame& f, int n) { int p = f.t0 + n; if (p >= f.RT) p -= f.RT; return f.tr[p]; }
+};
+
+template <class Src>
+__global__ __launch_bounds__(256) void k_dfa_features(Src src, int nframes, fft::Plan p1024, fft::Plan p640, const float2* __restrict__ tw1024, const float2* __restrict__ tw640,
                                                       const float* __restrict__ win_k, const float* __restrict__ win_a, BandTab mel, float2* __restrict__ spec,
                                                       float* __restrict__ feat) {
     __shared__ float2 A[kNK];
@@ -68,11 +107,10 @@ __global__ __launch_bounds__(256) void k_dfa_features(const int16_t* __restrict_
     for (int g = 0; g < kGroup; ++g) {
         const int fr = (int)blockIdx.x * kGroup + g;
         if (fr >= nframes) break;                // uniform over the workgroup
-        const int row = fr / Tm, t = fr - row * Tm, call = row / n_win, w = row - call * n_win;
-        const size_t at_near = ((size_t)call * 2 * n_win + w) * W + (size_t)t * kHA, at_temp = (size_t)row * W + (size_t)t * kHA;
+        const auto frame = src.frame(fr);
         double part[2] = {0.0, 0.0};
         for (int n = tid; n < kNA; n += 256) {
-            const float a = (fpcm ? fpcm[at_near + n] : (float)pcm[at_near + n]) * (1.0f / 32768.0f), b = temp[at_temp + n];
+            const float a = Src::near(frame, n), b = Src::temp_aec(frame, n);
             xs[n] = make_float2(a, b);
             part[0] += (double)a;
             part[1] += (double)b;
@@ -181,6 +219,110 @@ __global__ __launch_bounds__(256) void k_dfa_ola(const float* __restrict__ frame
     if (pcm) pcm[i] = (int16_t)(int)fminf(fmaxf(y * 32767.0f, -32768.0f), 32767.0f);          // .to(torch.int16): truncation
 }
 
+// ---- streams ----------------------------------------------------------------------------------------------------------------------------------------------------
+// After k hops of input the back end has nt = 256 max(0, k - 3) final temp_aec samples, M(k) = 0 if nt < 640, else (nt - 640) / 320 + 1 mask frames are complete and
+// 320 M(k) output samples are final; 320 M(k) >= 256 k - 1344 (include/ade.h has the derivation).
+constexpr int kDelay = 1344, kPend = 256;       // output lag in samples; the most final samples a push can leave for the next one (320 M(k) - (256 k - 1344) <= 256)
+constexpr int kNearLag = 1408, kTempLag = 640;  // samples a ring holds beyond one step: 256 k - 320 M(k) < 1408, nt(k) - 320 M(k) < 640
+
+// The step's new samples into the rings: near-end sample q of the push (channel 0 of the caller's [stream][2][P] rows; null in the flush) at (near_off + q) % RN,
+// temp_aec sample q of the back end's step ([stream][Pt]) at (temp_off + q) % RT for q >= t_min (the samples before the signal's first are skipped).
+__global__ __launch_bounds__(256) void k_dfa_stream_stage(const int16_t* __restrict__ pcm, const float* __restrict__ temp, int P, int Pt, int t_min, int16_t* __restrict__ near_ring,
+                                                          float* __restrict__ temp_ring, int RN, int RT, int near_off, int temp_off, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int span = P + Pt, st = (int)(i / span), q = (int)(i - (long long)st * span);
+    if (q < P) near_ring[(size_t)st * RN + (near_off + q) % RN] = pcm[(size_t)st * 2 * P + q];
+    else if (q - P >= t_min) temp_ring[(size_t)st * RT + (temp_off + (q - P)) % RT] = temp[(size_t)st * Pt + (q - P)];
+}
+
+// k_dfa_memory over the Mp frames a push completes, column j = stream * Mp + i.  A tap that reaches before the push reads the layer's history, hist_in [c][stream][Hl]:
+// the Hl = dil (lo - 1) frames before the push, oldest first, zeros before the stream's first frame (the reset's memset).  The taps are summed in k_dfa_memory's order.
+// The threads from `total` on write the next history into hist_out: the last Hl frames of [history | push].
+// Not promised: the one-shot call's bits.  k_dfa_memory adds a literal 0 for a tap before the window's first frame, this kernel w * (a history value, zero before the
+// stream's first frame), and the compiler may contract the two forms differently; the contract is the family's gates (1e-4, 1 LSB) against the one call on the whole
+// signal, and bit identity between push sizes, which only needs this kernel to agree with itself.
+__global__ __launch_bounds__(256) void k_dfa_stream_memory(const float* __restrict__ h, const float* __restrict__ w, float* __restrict__ x, const float* __restrict__ hist_in,
+                                                           float* __restrict__ hist_out, int S, int Mp, int Hl, int lo, int dil, int skip, long long total, long long total_all) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total_all) return;
+    const int N = S * Mp;
+    if (i < total) {
+        const int c = (int)(i / N), j = (int)(i - (long long)c * N), st = j / Mp, t = j - st * Mp;
+        const float* row = h + (size_t)c * N + j;
+        const float* old = hist_in + ((size_t)c * S + st) * Hl + Hl + t;          // old[dt]: frame t + dt of the push, t + dt < 0
+        float s = 0.0f;
+        for (int k = 0; k < lo; ++k) {
+            const int dt = (k - (lo - 1)) * dil;
+            const float v = t + dt >= 0 ? row[dt] : old[dt];
+            s += w[c * lo + k] * v;
+        }
+        if (skip) s += row[0];
+        x[i] += s;
+        return;
+    }
+    const long long e = i - total;                                                // (c, stream, slot): slot q holds frame Mp - Hl + q of the push
+    const int q = (int)(e % Hl), cs = (int)(e / Hl), c = cs / S, st = cs - c * S, t = Mp - Hl + q;
+    hist_out[e] = t >= 0 ? h[(size_t)c * N + (size_t)st * Mp + t] : hist_in[(size_t)cs * Hl + (Hl + t)];
+}
+
+// One workgroup per frame: mask * spectrum -> the Hermitian inverse 640-point transform of ONE frame -> * symmetric hamming / 640.  The last frame of a stream's push
+// also leaves its second half in half_out [stream][320], which the next push's overlap-add starts from.
+__global__ __launch_bounds__(256) void k_dfa_stream_synthesis(const float2* __restrict__ spec, const float* __restrict__ mask, int Mp, fft::Plan p640, const float2* __restrict__ tw640,
+                                                              const float* __restrict__ win, float* __restrict__ frames, float* __restrict__ half_out) {
+    __shared__ float2 A[kNA];
+    __shared__ float2 B[kNA];
+    const int tid = threadIdx.x, fr = (int)blockIdx.x, st = fr / Mp, i = fr - st * Mp;
+    for (int f = tid; f < kFA; f += 256) {
+        const bool edge = f == 0 || f == kFA - 1;
+        const float m = mask[(size_t)fr * kFA + f];
+        const float2 sp = spec[(size_t)fr * kFA + f];
+        const float re = sp.x * m, im = edge ? 0.0f : sp.y * m;
+        A[f] = make_float2(re, -im);
+        if (!edge) A[kNA - f] = make_float2(re, im);
+    }
+    const float2* r = fft::forward(A, B, p640, tw640, tid, 256);
+    for (int n = tid; n < kNA; n += 256) {
+        const float v = (r[n].x * (1.0f / (float)kNA)) * win[n];
+        frames[(size_t)fr * kNA + n] = v;
+        if (i == Mp - 1 && n >= kHA) half_out[(size_t)st * kHA + (n - kHA)] = v;
+    }
+}
+
+// Output of a step.  Positions are counted from the first sample of the push's first frame (signal sample 320 M0): output sample q of the step is position e_rel + q.
+//   position < 0     final since an earlier push: pend_in[stream][q] for q < n_pend, else before the signal's first sample, zero
+//   position r >= 0  frame r / 320 of the push and the frame before it, added in ascending frame order (k_dfa_ola's); the frame before the push's first is half_in
+//                    (has_prev), and nothing at the signal's first frame
+// times the one-shot's 1 / window-square table: its head entries for the signal's first 320 samples (head), its tail entries from position tail_from on (the flush:
+// the signal's last 320 samples), its steady entries 320 .. 639 otherwise.  The threads q >= Pout write the kPend samples behind the step into pend_out, zero where
+// they are not final yet (pend_out null: the flush).
+__global__ __launch_bounds__(256) void k_dfa_stream_out(const float* __restrict__ frames, const float* __restrict__ half_in, const float* __restrict__ pend_in, float* __restrict__ pend_out,
+                                                        const float* __restrict__ inv_ws, int W, int Mp, int Pout, int e_rel, int n_pend, int has_prev, int head, int tail_from,
+                                                        int16_t* __restrict__ pcm, float* __restrict__ f32, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int span = Pout + (pend_out ? kPend : 0), st = (int)(i / span), q = (int)(i - (long long)st * span), r = e_rel + q;
+    float y = 0.0f;
+    if (r < 0) {
+        if (q < n_pend) y = pend_in[(size_t)st * kPend + q];
+    } else if (r < kHA * Mp + (q < Pout ? kHA : 0)) {                     // (an emitted sample is always final; one kept for later only inside the completed frames)
+        const int fi = r / kHA, n = r - fi * kHA;
+        float s = 0.0f;
+        if (fi > 0) s += frames[((size_t)st * Mp + fi - 1) * kNA + kHA + n];
+        else if (has_prev) s += half_in[(size_t)st * kHA + n];
+        if (fi < Mp) s += frames[((size_t)st * Mp + fi) * kNA + n];
+        const int at = head && r < kHA ? r : (r >= tail_from ? W - kHA + n : kHA + n);
+        y = s * inv_ws[at];
+    }
+    if (q >= Pout) {
+        pend_out[(size_t)st * kPend + (q - Pout)] = y;
+        return;
+    }
+    const size_t o = (size_t)st * Pout + q;
+    if (f32) f32[o] = y;
+    if (pcm) pcm[o] = (int16_t)(int)fminf(fmaxf(y * 32767.0f, -32768.0f), 32767.0f);          // .to(torch.int16): truncation
+}
+
 void hamming_symmetric_f32(int n, std::vector<float>& w) {      // torch.hamming_window(n, periodic=False) as evaluated in fp32
     w.resize((size_t)n);
     const float step = (float)(2.0 * M_PI / (double)(n - 1));
@@ -226,6 +368,33 @@ struct DfsmnAecEngine : SubEngine {
     int reserve(int batch, std::string& err) override;
     int run(hipStream_t s, const int16_t* d_in, int batch, int16_t* d_out, float* d_f32, std::string& err) override;
     int tap(hipStream_t s, const char* name, int batch, float* out, size_t count, size_t* written, std::string& err) override;
+    // streams (ade_stream_*): state per stream object, see DfaStream below.  Audio only: the speech-probability head is not evaluated.
+    int stream_delay() const override { return kDelay; }
+    int stream_create(int n_streams, int frames_per_push, void** state, std::string& err) override;
+    int stream_reset(void* state, hipStream_t s, std::string& err) override;
+    int stream_push(void* state, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) override;
+    int stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) override;
+    void stream_destroy(void* state) override;
+    int stream_step(struct DfaStream* st, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err);
+};
+
+// What a stream carries between pushes, for S streams that advance together: one allocation, its leading part cleared by a reset.
+struct DfaStream {
+    int S = 0, F = 0, Mmax = 0;                 // streams, hops per push, the most mask frames one step completes
+    long long hops = 0;                         // hops pushed since the last reset
+    void* nkf = nullptr;                        // the back end's own stream state
+    int RN = 0, RT = 0;
+    int16_t* near_ring = nullptr;               // [S][RN] near-end samples not yet consumed by a mask frame, sample a at a % RN
+    float* temp_ring = nullptr;                 // [S][RT] temp_aec samples not yet consumed, sample a at a % RT
+    float* hist[2] = {};                        // per layer [D][S][dilation (lorder - 1)]: the last frames of the projection output, ping-ponged
+    std::vector<size_t> hist_off;               // a layer's offset inside hist[.]
+    float* half[2] = {};                        // [S][320] the second half of the last synthesised frame, ping-ponged with hist (cur)
+    float* pend[2] = {};                        // [S][256] final output samples not yet emitted, ping-ponged every step (pcur)
+    int cur = 0, pcur = 0;
+    float *temp = nullptr, *feat = nullptr, *x = nullptr, *f1 = nullptr, *p1 = nullptr, *mask = nullptr, *frames = nullptr;     // one step's workspace
+    float2* spec = nullptr;
+    void* block = nullptr;
+    size_t reset_bytes = 0;
 };
 
 int dfsmn_aec_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, bool exact_dft, int device, SubEngine** out, std::string& err) {
@@ -387,8 +556,8 @@ int DfsmnAecEngine::run(hipStream_t s, const int16_t* d_in, int batch, int16_t* 
     st = nkf->run(s, d_in, float_in, batch, n_win, temp, err);
     if (st != ADE_OK) return st;
     // 2. Kaldi features of near / temp_aec / echo estimate and the mask transform of temp_aec               (:1288-1311)
-    hipLaunchKernelGGL(k_dfa_features, dim3((unsigned)((N + kGroup - 1) / kGroup)), dim3(256), 0, s, d_in, float_in, (const float*)temp, W, Tm, n_win, N, p1024, p640, tw1024,
-                       tw640, win_k, win_a, mel, spec, feat);
+    hipLaunchKernelGGL(k_dfa_features<CallSrc>, dim3((unsigned)((N + kGroup - 1) / kGroup)), dim3(256), 0, s, CallSrc{d_in, float_in, temp, W, Tm, n_win}, N, p1024, p640,
+                       tw1024, tw640, win_k, win_a, mel, spec, feat);
     // 3. the mask network                                                                                  (:1312-1320)
     launch(s, RowMajorA{lin1_w, kFeat}, FeatFrameB{feat}, BiasActStore<kActRelu>{x, N, lin1_b, 0.0f}, D, N, kFeat);
     for (const Layer& l : layers) {
@@ -424,6 +593,149 @@ int DfsmnAecEngine::tap(hipStream_t s, const char* name, int batch, float* out, 
     DA_HIP(hipMemcpy(out, src, n * sizeof(float), hipMemcpyDeviceToHost));
     *written = n;
     return ADE_OK;
+}
+
+// ---- streams ----------------------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+long long mask_frames_after(long long hops) {           // M(k): the mask frames complete after k hops of input
+    const long long nt = hops > 3 ? (hops - 3) * 256 : 0;
+    return nt < kNA ? 0 : (nt - kNA) / kHA + 1;
+}
+}  // namespace
+
+int DfsmnAecEngine::stream_create(int n_streams, int frames_per_push, void** state, std::string& err) {
+    *state = nullptr;
+    if (n_streams < 1 || frames_per_push < 1 || frames_per_push > 4096)
+        return afail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: dfsmn_aec needs n_streams >= 1 and 1 <= frames_per_push <= 4096");
+    const int P = frames_per_push * 256, Pmax = P > 768 ? P : 768;                    // the flush is a step of the back end's last 768 samples
+    const int Mmax = P / kHA + 1 > 3 ? P / kHA + 1 : 3;                               // the flush completes at most three frames
+    const size_t S = (size_t)n_streams, N = S * Mmax;
+    if (N * kNA > 0x7fffffffULL || S * (size_t)(Pmax + kNearLag) > 0x7fffffffULL)
+        return afail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: dfsmn_aec: n_streams * frames_per_push exceeds the launch grid");
+    std::unique_ptr<DfaStream> st(new DfaStream());
+    st->S = n_streams; st->F = frames_per_push; st->Mmax = Mmax;
+    st->RN = Pmax + kNearLag; st->RT = Pmax + kTempLag;
+    int rc = nkf->stream_create(n_streams, frames_per_push, &st->nkf, err);
+    if (rc != ADE_OK) return rc;
+    auto up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    size_t hist_floats = 0;
+    for (const Layer& l : layers) { st->hist_off.push_back(hist_floats); hist_floats += (size_t)D * S * l.dilation * (l.lorder - 1); }
+    const size_t b_near = up(S * st->RN * sizeof(int16_t)), b_temp = up(S * st->RT * sizeof(float)), b_hist = up(hist_floats * sizeof(float)), b_half = up(S * kHA * sizeof(float)),
+                 b_pend = up(S * kPend * sizeof(float));
+    const size_t work[8] = {up(S * Pmax * sizeof(float)), up(N * kFA * sizeof(float2)), up(N * kFeat * sizeof(float)), up((size_t)D * N * sizeof(float)),
+                            up((size_t)Hmax * N * sizeof(float)), up((size_t)D * N * sizeof(float)), up(N * kFA * sizeof(float)), up(N * kNA * sizeof(float))};
+    size_t total = b_near + b_temp + 2 * b_hist + 2 * b_half + 2 * b_pend;
+    st->reset_bytes = total;
+    for (size_t b : work) total += b;
+    if (hipSetDevice(device) != hipSuccess || hipMalloc(&st->block, total) != hipSuccess) {
+        nkf->stream_destroy(st->nkf);
+        return afail(err, ADE_ERR_DEVICE, "ade_stream_create: hipMalloc of the DFSMN-AEC stream state failed");
+    }
+    char* p = (char*)st->block;
+    st->near_ring = (int16_t*)p; p += b_near;
+    st->temp_ring = (float*)p; p += b_temp;
+    for (int i = 0; i < 2; ++i) { st->hist[i] = (float*)p; p += b_hist; }
+    for (int i = 0; i < 2; ++i) { st->half[i] = (float*)p; p += b_half; }
+    for (int i = 0; i < 2; ++i) { st->pend[i] = (float*)p; p += b_pend; }
+    st->temp = (float*)p; p += work[0];
+    st->spec = (float2*)p; p += work[1];
+    st->feat = (float*)p; p += work[2];
+    st->x = (float*)p; p += work[3];
+    st->f1 = (float*)p; p += work[4];
+    st->p1 = (float*)p; p += work[5];
+    st->mask = (float*)p; p += work[6];
+    st->frames = (float*)p;
+    *state = st.release();
+    return ADE_OK;
+}
+
+int DfsmnAecEngine::stream_reset(void* state, hipStream_t s, std::string& err) {
+    DfaStream* st = (DfaStream*)state;
+    const int rc = nkf->stream_reset(st->nkf, s, err);
+    if (rc != ADE_OK) return rc;
+    DA_HIP(hipMemsetAsync(st->block, 0, st->reset_bytes, s));
+    st->hops = 0;
+    st->cur = 0;
+    st->pcur = 0;
+    return ADE_OK;
+}
+
+// One step: a push of F hops (d_in set), or the flush (d_in null: the back end's last 768 temp_aec samples, the remaining mask frames, 1344 output samples).
+int DfsmnAecEngine::stream_step(DfaStream* st, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) {
+    using namespace gemm;
+    const bool flush = d_in == nullptr;
+    const int S = st->S, P = flush ? 0 : st->F * 256, Pt = flush ? 768 : P, Pout = flush ? kDelay : P;
+    const long long k0 = st->hops, k1 = k0 + (flush ? 0 : st->F);
+    const long long M0 = mask_frames_after(k0), M1 = flush ? (k0 * 256 - kNA) / kHA + 1 : mask_frames_after(k1);
+    const int Mp = (int)(M1 - M0), N = S * Mp;
+    // 1. the linear canceller: the step's temp_aec samples, signal samples 256 k0 - 768 onwards
+    int rc = flush ? nkf->stream_flush(st->nkf, s, st->temp, err) : nkf->stream_step(st->nkf, s, d_in, st->temp, err);
+    if (rc != ADE_OK) return rc;
+    // 2. into the rings, addressed by the signal's sample index
+    const long long t_first = k0 * 256 - 768;                                             // signal index of the step's first temp_aec sample (negative: not a sample)
+    const int t_min = t_first < 0 ? (int)-t_first : 0;
+    {
+        const long long total = (long long)S * (P + Pt);
+        hipLaunchKernelGGL(k_dfa_stream_stage, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_in, (const float*)st->temp, P, Pt, t_min, st->near_ring, st->temp_ring,
+                           st->RN, st->RT, (int)((k0 * 256) % st->RN), (int)(((t_first % st->RT) + st->RT) % st->RT), total);
+    }
+    const int nxt = st->cur ^ 1;
+    if (Mp > 0) {
+        // 3. features and the mask transform of the frames this step completes
+        const RingSrc src{st->near_ring, st->temp_ring, Mp, st->RN, st->RT, (int)((M0 * kHA) % st->RN), (int)((M0 * kHA) % st->RT)};
+        hipLaunchKernelGGL(k_dfa_features<RingSrc>, dim3((unsigned)((N + kGroup - 1) / kGroup)), dim3(256), 0, s, src, N, p1024, p640, tw1024, tw640, win_k, win_a, mel, st->spec,
+                           st->feat);
+        // 4. the mask network, the memory continued from each layer's history
+        launch(s, RowMajorA{lin1_w, kFeat}, FeatFrameB{st->feat}, BiasActStore<kActRelu>{st->x, N, lin1_b, 0.0f}, D, N, kFeat);
+        for (size_t li = 0; li < layers.size(); ++li) {
+            const Layer& l = layers[li];
+            launch(s, RowMajorA{l.lin_w, D}, RowMajorB{st->x, N}, BiasActStore<kActRelu>{st->f1, N, l.lin_b, 0.0f}, l.H, N, D);
+            launch(s, RowMajorA{l.proj_w, l.H}, RowMajorB{st->f1, N}, BiasActStore<kActNone>{st->p1, N, nullptr, 0.0f}, D, N, l.H);
+            const int Hl = l.dilation * (l.lorder - 1);
+            const long long total = (long long)D * N, total_all = total + (long long)D * S * Hl;
+            hipLaunchKernelGGL(k_dfa_stream_memory, dim3((unsigned)((total_all + 255) / 256)), dim3(256), 0, s, (const float*)st->p1, l.conv_w, st->x,
+                               (const float*)(st->hist[st->cur] + st->hist_off[li]), st->hist[nxt] + st->hist_off[li], S, Mp, Hl, l.lorder, l.dilation, l.skip, total, total_all);
+        }
+        launch(s, RowMajorA{lin2_w, D}, RowMajorB{st->x, N}, MaskTStore{st->mask, lin2_b}, kFA, N, D);
+        // 5. one inverse transform per frame
+        hipLaunchKernelGGL(k_dfa_stream_synthesis, dim3((unsigned)N), dim3(256), 0, s, (const float2*)st->spec, (const float*)st->mask, Mp, p640, tw640, win_a, st->frames,
+                           st->half[nxt]);
+    }
+    // 6. overlap-add, norm, the samples kept for the next step, PCM tail
+    {
+        const long long e_first = k0 * 256 - kDelay;                                      // signal index of the step's first output sample
+        const int e_rel = (int)(e_first - M0 * kHA), n_pend = M0 > 0 ? -e_rel : 0;
+        const long long total = (long long)S * (Pout + (flush ? 0 : kPend));
+        hipLaunchKernelGGL(k_dfa_stream_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)st->frames, (const float*)st->half[st->cur],
+                           (const float*)st->pend[st->pcur], flush ? (float*)nullptr : st->pend[st->pcur ^ 1], inv_ws, W, Mp, Pout, e_rel, n_pend, M0 > 0 ? 1 : 0, M0 == 0 ? 1 : 0,
+                           flush ? Mp * kHA : 0x7fffffff, d_out, d_f32, total);
+    }
+    DA_HIP(hipGetLastError());
+    if (Mp > 0) st->cur = nxt;
+    st->pcur ^= 1;
+    st->hops = k1;
+    return ADE_OK;
+}
+
+int DfsmnAecEngine::stream_push(void* state, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) {
+    return stream_step((DfaStream*)state, s, d_in, d_out, d_f32, err);
+}
+
+int DfsmnAecEngine::stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) {
+    DfaStream* st = (DfaStream*)state;
+    if (st->hops < 5 || st->hops % 5)
+        return afail(err, ADE_ERR_BAD_VALUE, "ade_stream_flush: dfsmn_aec ends a signal only where the reference's static export accepts its length, a multiple of 320 samples: "
+                                             "the hops pushed must be a multiple of 5, at least 5 (pushed: " + std::to_string(st->hops) + ")");
+    return stream_step(st, s, nullptr, d_out, d_f32, err);
+}
+
+void DfsmnAecEngine::stream_destroy(void* state) {
+    DfaStream* st = (DfaStream*)state;
+    if (!st) return;
+    (void)hipSetDevice(device);
+    if (st->nkf) nkf->stream_destroy(st->nkf);
+    if (st->block) (void)hipFree(st->block);
+    delete st;
 }
 
 }  // namespace ade

@@ -311,6 +311,14 @@ struct NkfBackend {
     virtual int frames() const = 0;
     virtual int reserve(int windows, std::string& err) = 0;
     virtual int run(hipStream_t s, const int16_t* pcm, const float* fpcm, int calls, int n_win, float* wave, std::string& err) = 0;
+    // Streams: the stream kernels of csrc/ade_nkf_aec.hip on the caller's [stream][near end, far end][frames_per_push * 256] int16 rows.  A step leaves the float
+    // waveform of its frames_per_push * 256 output samples, 768 samples behind the input, in wave ([stream][frames_per_push * 256]); the flush the last 768 samples
+    // ([stream][768]).  Everything is enqueued on `s`; the state is one allocation, a reset one memset.
+    virtual int stream_create(int n_streams, int frames_per_push, void** state, std::string& err) = 0;
+    virtual int stream_reset(void* state, hipStream_t s, std::string& err) = 0;
+    virtual int stream_step(void* state, hipStream_t s, const int16_t* pcm, float* wave, std::string& err) = 0;
+    virtual int stream_flush(void* state, hipStream_t s, float* wave, std::string& err) = 0;
+    virtual void stream_destroy(void* state) = 0;
 };
 // reference_tables: the two transforms as dense products with the reference's fp32-angle DFT tables instead of the FFT kernels (see csrc/ade_nkf_aec.hip, DenseFrameB).
 int nkf_backend_create(const std::map<std::string, Tensor>& tensors, int window_len, bool reference_tables, int device, NkfBackend** out, std::string& err) __attribute__((weak));

@@ -295,9 +295,11 @@ constexpr int kCarry = 3 * kHopN;
 // one workgroup per (stream, frame): the far-end and the near-end frame OF THE SAME INDEX as one complex transform.  Pairing frames (t, t + 1) as the one-shot
 // kernel does would make a frame's rounding depend on where the push boundary falls (the two halves of a packed transform share rounding cross-talk); the two
 // channels of a frame always arrive together.  The last workgroup of a stream (frame index T) moves the rows' last 768 samples into the OTHER carry buffer.
-// pcm null (flush): the new samples are zeros, no carry is kept.
+// pcm null (flush): the new samples are zeros, no carry is kept.  swap (the back end of dfsmn_aec): the caller's channel 0 is the near end, so the far-end frame is
+// read from source channel 1; the carries keep the caller's order.  T = 0 with a carry_out: only the carry moves (the dense-table back end frames its rows itself).
 __global__ __launch_bounds__(256) void k_nkf_stream_analysis(const int16_t* __restrict__ pcm, const int16_t* __restrict__ carry_in, int16_t* __restrict__ carry_out, int P, int T,
-                                                             int off0, fft::Plan plan, const float2* __restrict__ tw, const float* __restrict__ win, float2* __restrict__ spec) {
+                                                             int off0, fft::Plan plan, const float2* __restrict__ tw, const float* __restrict__ win, float2* __restrict__ spec,
+                                                             int swap) {
     __shared__ float2 A[kN];
     __shared__ float2 Bf[kN];
     const int tid = threadIdx.x, per = T + (carry_out ? 1 : 0), st = (int)blockIdx.x / per, j = (int)blockIdx.x - st * per;
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(256) void k_nkf_stream_analysis(const int16_t* __re
         return;
     }
     const int o = off0 + j * kHopN;
-    for (int n = tid; n < kN; n += 256) A[n] = make_float2((float)row(0, o + n) * win[n], (float)row(1, o + n) * win[n]);
+    for (int n = tid; n < kN; n += 256) A[n] = make_float2((float)row(swap, o + n) * win[n], (float)row(1 - swap, o + n) * win[n]);
     const float2* r = fft::forward(A, Bf, plan, tw, tid, 256);
     float2* far = spec + ((size_t)st * 2 * T + j) * kF;
     float2* near = far + (size_t)T * kF;
@@ -452,6 +454,30 @@ struct DenseFrameStore {
     float* p;
     __device__ void operator()(int m, int n, float v) const { p[(size_t)n * kN + m] = v; }
 };
+// The same two products over a stream's step: column n = (stream * 2 + channel) * T + j is frame j of the step, read from the rows [768 carried | P new] as
+// k_nkf_stream_analysis reads them (pcm null: the flush's zeros; swap: channel 0 of the spectra, the far end, is source channel 1) ...
+struct DenseStreamFrameB {
+    static constexpr bool kAlongN = false;
+    const int16_t* pcm;
+    const int16_t* carry;
+    int P, T, off0, swap;
+    __device__ float operator()(int k, int n) const {
+        const int row = n / T, j = n - row * T, st = row >> 1, ch = swap ? 1 - (row & 1) : (row & 1), p = off0 + j * kHopN + k;
+        int v = 0;
+        if (p < kCarry) v = carry[((size_t)st * 2 + ch) * kCarry + p];
+        else if (pcm && p - kCarry < P) v = pcm[((size_t)st * 2 + ch) * P + (p - kCarry)];
+        return (float)v * (1.0f / 32768.0f);
+    }
+};
+// ... and error frame n = stream * T + j stored into slot base + j of the stream's frame row (k_nkf_stream_synthesis's layout)
+struct DenseStreamFrameStore {
+    float* p;
+    int T, base, slots;
+    __device__ void operator()(int m, int n, float v) const {
+        const int st = n / T, j = n - st * T;
+        p[((size_t)st * slots + base + j) * kN + m] = v;
+    }
+};
 
 }  // namespace
 
@@ -491,6 +517,7 @@ struct NkfAecEngine : SubEngine {
     int stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) override;
     void stream_destroy(void* state) override;
     int stream_step(struct NkfStream* st, hipStream_t s, const int16_t* d_in, int hops, int16_t* d_out, float* d_f32, std::string& err);
+    bool near_first = false;                    // the back end of dfsmn_aec: the caller's rows are (near end, far end)
     const float *dense_fwd = nullptr, *dense_inv = nullptr;      // [1026][1024] each, the reference's fp32-angle tables (back end with reference_tables only)
     int run_backend(hipStream_t s, const int16_t* pcm, const float* fpcm, int calls, int n_win, float* wave, std::string& err);
 };
@@ -562,6 +589,7 @@ static int nkf_build(const std::map<std::string, Tensor>& tensors, int in_len, i
     d->L = in_len;
     d->T = in_len / kHopN + 1;                                       // MAX_SIGNAL_LENGTH (:35)
     d->keep = kHopN * (d->T - 1) < in_len ? kHopN * (d->T - 1) : in_len;     // the ISTFT's trimmed length, then [:audio_len] (:389)
+    d->near_first = backend;
     if (backend) d->keep = in_len;                                   // 512 + in_len <= 1024 + 256 (T - 1): inside the raw overlap-add
     // periodic hann as torch.hann_window builds it in fp32; the 2^-15 input scale of an int16 export folded into the analysis window (:485)
     std::vector<float> hann(kN);
@@ -628,6 +656,11 @@ struct NkfBackendImpl : NkfBackend {
     int run(hipStream_t s, const int16_t* pcm, const float* fpcm, int calls, int n_win, float* wave, std::string& err) override {
         return e->run_backend(s, pcm, fpcm, calls, n_win, wave, err);
     }
+    int stream_create(int n_streams, int frames_per_push, void** state, std::string& err) override { return e->stream_create(n_streams, frames_per_push, state, err); }
+    int stream_reset(void* state, hipStream_t s, std::string& err) override { return e->stream_reset(state, s, err); }
+    int stream_step(void* state, hipStream_t s, const int16_t* pcm, float* wave, std::string& err) override { return e->stream_push(state, s, pcm, nullptr, wave, err); }
+    int stream_flush(void* state, hipStream_t s, float* wave, std::string& err) override { return e->stream_flush(state, s, nullptr, wave, err); }
+    void stream_destroy(void* state) override { e->stream_destroy(state); }
 };
 }  // namespace
 
@@ -776,18 +809,39 @@ int NkfAecEngine::stream_reset(void* state, hipStream_t s, std::string& err) {
     return ADE_OK;
 }
 
-// One step: `hops` new hops of input (d_in null: zeros past the end of the signal, the flush).  Analysis, Kalman, synthesis, overlap-add: four launches.
+// One step: `hops` new hops of input (d_in null: zeros past the end of the signal, the flush).  Analysis, Kalman, synthesis, overlap-add: four launches (six with the
+// reference's tables, the back end of dfsmn_aec in its default mode: each transform is a dense product plus the kernel that moves what is carried).
 int NkfAecEngine::stream_step(NkfStream* st, hipStream_t s, const int16_t* d_in, int hops, int16_t* d_out, float* d_f32, std::string& err) {
     const bool first = st->hops == 0, flush = d_in == nullptr;
     const int S = st->S, P = hops * kHopN, T = first ? hops - 1 : hops, base = first ? 4 : 3, nxt = st->cur ^ 1;
     const int out = flush ? kCarry : P;                                                  // the flush emits the 768 samples still owed
     const int young = st->hops < 4 ? (int)st->hops : 4;                                  // slot j holds frame hops - 4 + j
-    hipLaunchKernelGGL(k_nkf_stream_analysis, dim3((unsigned)(S * (T + (flush ? 0 : 1)))), dim3(256), 0, s, d_in, (const int16_t*)st->carry[st->cur],
-                       flush ? (int16_t*)nullptr : st->carry[nxt], P, T, first ? kHopN : 0, plan, tw, win, st->spec);
+    const int swap = near_first ? 1 : 0;
+    const int16_t* carry = st->carry[st->cur];
+    int16_t* carry_next = flush ? (int16_t*)nullptr : st->carry[nxt];
+    const float* prev = first ? (const float*)nullptr : (const float*)st->frames[st->cur];
+    if (dense_fwd) {          // the reference's tables: the frames of the step as one dense product, the carry moved by the analysis kernel run without frames
+        if (T > 0)
+            gemm::launch(s, gemm::RowMajorA{dense_fwd, kN}, DenseStreamFrameB{d_in, carry, P, T, first ? kHopN : 0, swap}, DenseSpecStore{reinterpret_cast<float*>(st->spec)},
+                         2 * kF, S * 2 * T, kN);
+        if (!flush)
+            hipLaunchKernelGGL(k_nkf_stream_analysis, dim3((unsigned)S), dim3(256), 0, s, d_in, carry, carry_next, P, 0, 0, plan, tw, win, st->spec, swap);
+    } else {
+        hipLaunchKernelGGL(k_nkf_stream_analysis, dim3((unsigned)(S * (T + (flush ? 0 : 1)))), dim3(256), 0, s, d_in, carry, carry_next, P, T, first ? kHopN : 0, plan, tw,
+                           win, st->spec, swap);
+    }
     hipLaunchKernelGGL(k_nkf_kalman<true>, dim3((unsigned)((S * kF + kKalmanThreads - 1) / kKalmanThreads)), dim3(kKalmanThreads), 0, s, (const float2*)st->spec, wts, T, S,
                        st->errs, (float2*)nullptr, st->kalman);
-    hipLaunchKernelGGL(k_nkf_stream_synthesis, dim3((unsigned)(S * (base + T))), dim3(256), 0, s, (const float2*)st->errs, T, base, st->slots,
-                       first ? (const float*)nullptr : (const float*)st->frames[st->cur], st->prev_off, plan, tw, syn_win, st->frames[nxt]);
+    if (dense_inv) {          // the carried slots copied by the synthesis kernel run without frames, the new ones stored by the product
+        hipLaunchKernelGGL(k_nkf_stream_synthesis, dim3((unsigned)(S * base)), dim3(256), 0, s, (const float2*)st->errs, 0, base, st->slots, prev, st->prev_off, plan, tw,
+                           syn_win, st->frames[nxt]);
+        if (T > 0)
+            gemm::launch(s, DenseInvA{dense_inv}, DenseErrB{reinterpret_cast<const float*>(st->errs)}, DenseStreamFrameStore{st->frames[nxt], T, base, st->slots}, kN, S * T,
+                         2 * kF);
+    } else {
+        hipLaunchKernelGGL(k_nkf_stream_synthesis, dim3((unsigned)(S * (base + T))), dim3(256), 0, s, (const float2*)st->errs, T, base, st->slots, prev, st->prev_off, plan,
+                           tw, syn_win, st->frames[nxt]);
+    }
     const long long total = (long long)S * out;
     hipLaunchKernelGGL(k_nkf_stream_ola, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)st->frames[nxt], win2, st->slots, 4 - young, base + T - 1,
                        kCarry - young * kHopN > 0 ? kCarry - young * kHopN : 0, out, d_out, d_f32, total);

@@ -14,7 +14,9 @@ The VAD post-processing works on the per-frame speech probabilities of the frame
   2. runs of speech become (start, end) pairs, the end one frame shift after the first silent frame (:func:`segments`);
   3. segments shorter than ``min_speech_duration`` are dropped, then neighbours at most ``fusion_threshold`` apart are merged (:func:`fuse_segments`).
 
-    python -m audio_denoiser_onnx_amd.inference_dfsmn_aec <model_dir_or_.adew> [near.wav far.wav out.wav] [--normalize]
+    python -m audio_denoiser_onnx_amd.inference_dfsmn_aec <model_dir_or_.adew> [near.wav far.wav out.wav] [--normalize] [--stream N]
+
+``--stream N``: one stateful stream over the whole file in pushes of at most N hops (:func:`process_streaming`) instead of independent windows; audio only.
 
 The default inputs are the reference's example clips, ``<ADE_TEST_EXAMPLES or ./Test_Examples>/aec/{nearend_mic1,farend_speech1}.wav``.
 """
@@ -160,6 +162,36 @@ def process(sess, near: np.ndarray, far: np.ndarray, normalize: bool = False, rn
     return audio, stamps
 
 
+def process_streaming(sess, near: np.ndarray, far: np.ndarray, frames_per_push: int = 62, normalize: bool = False) -> np.ndarray:
+    """Whole int16 signals -> the echo-cancelled int16 signal through ONE stateful stream (``--stream N``).
+
+    :func:`process` -- like the reference's driver -- restarts the Kalman filter and zeroes the mask network's memory in every window of the graph's static
+    length.  Here both are carried on the device from push to push, so the canceller keeps the echo path it has learnt over the whole file; the result is what the
+    reference's unfolded graph gives on the whole (padded) file in one call.  Audio only: a stream returns no speech probabilities.
+
+    Both signals are trimmed to the shorter one and zero-padded at the end to a multiple of 1280 samples (whole hops of 256 AND a length the reference's static
+    export accepts, a multiple of 320: the flush is defined only there), and pushed in pushes of the largest number of hops that divides the padded hop count and
+    does not exceed ``frames_per_push``.  The stream's latency (1344 samples: the first ``delay`` samples of pushes + flush are dropped) is removed again and the
+    output cut to the input length.  The session's own static length, folded or not, does not matter."""
+    from .session import StreamingSession
+    if getattr(sess, "in_dtype", np.int16) != np.int16 or getattr(sess, "out_dtype", np.int16) != np.int16:
+        raise ValueError("inference_dfsmn_aec: a stream takes and returns int16 PCM; export the model with INT16 audio tensors")
+    if int(frames_per_push) < 1:
+        raise ValueError("inference_dfsmn_aec: frames_per_push must be at least 1")
+    near, far = normalise_audio(near, normalize), normalise_audio(far, normalize)
+    n = min(len(near), len(far))
+    hops = 5 * max(1, -(-n // 1280))
+    per_push = max(d for d in range(1, min(int(frames_per_push), hops) + 1) if hops % d == 0)
+    P, n_push = per_push * 256, hops // per_push
+    rows = np.zeros((1, 2, hops * 256), np.int16)
+    rows[0, 0, :n], rows[0, 1, :n] = near[:n], far[:n]                 # this family's order: near end, far end
+    with StreamingSession(sess, 1, per_push) as st:
+        parts = [st.push(rows[:, :, i * P:(i + 1) * P]) for i in range(n_push)]
+        parts.append(st.flush())
+        delay = st.delay
+    return np.ascontiguousarray(np.concatenate(parts, axis=1)[0, delay:delay + n])
+
+
 def write_timestamps(stamps, directory, in_rate: int = 16000) -> None:
     directory = Path(directory)
     with open(directory / "timestamps_second.txt", "w", encoding="utf-8") as f:
@@ -170,11 +202,11 @@ def write_timestamps(stamps, directory, in_rate: int = 16000) -> None:
             f.write(f"{round(a * in_rate)} --> {round(b * in_rate)}\n")
 
 
-def main(sess, near_path=None, far_path=None, out_path: str = "aec.wav", normalize: bool = False, rng=None):
+def main(sess, near_path=None, far_path=None, out_path: str = "aec.wav", normalize: bool = False, rng=None, stream: int = 0):
     in_rate, out_rate = session_rates(sess)
     near = read_wav_int16(near_path or example_audio("aec", "nearend_mic1.wav"), in_rate)
     far = read_wav_int16(far_path or example_audio("aec", "farend_speech1.wav"), in_rate)
-    y, stamps = process(sess, near, far, normalize, rng)
+    y, stamps = (process_streaming(sess, near, far, stream, normalize), None) if stream else process(sess, near, far, normalize, rng)
     if y.dtype == np.int16:
         write_wav_int16(out_path, y, out_rate)
     else:
@@ -186,11 +218,16 @@ def main(sess, near_path=None, far_path=None, out_path: str = "aec.wav", normali
 
 if __name__ == "__main__":
     from .session import InferenceSession
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv, stream = list(sys.argv[1:]), 0
+    if "--stream" in argv:                     # --stream N: one stateful stream, pushes of at most N hops (process_streaming)
+        i = argv.index("--stream")
+        stream = int(argv[i + 1])
+        del argv[i:i + 2]
+    args = [a for a in argv if not a.startswith("--")]
     if len(args) not in (1, 4):
         print(__doc__)
         raise SystemExit(2)
     s = InferenceSession(args[0])
     paths = args[1:] if len(args) == 4 else (None, None, "aec.wav")
-    main(s, *paths, normalize="--normalize" in sys.argv)
+    main(s, *paths, normalize="--normalize" in sys.argv, stream=stream)
     print(f"AEC done: {paths[2]}")

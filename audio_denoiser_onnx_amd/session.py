@@ -96,6 +96,7 @@ class InferenceSession:
         tname = {np.int16: "tensor(int16)", np.float32: "tensor(float)", np.float16: "tensor(float16)"}
         family = reader.string("model_family", "")
         self._aec = family in ("nkf_aec", "dfsmn_aec")
+        self._aec_near_first = family == "dfsmn_aec"      # the order of the engine's two planar rows, and of a stream's
         # DFSMN-AEC's optional second output: one speech probability per mask frame of every window of the call, float32 (B * windows * frames,) (:1317-1319, :1520)
         self._vad = family == "dfsmn_aec" and bool(reader.optional_bool("output_vad_result", False))
         if self._aec:      # two graph inputs, one channel each: channels 0 and 1 of the engine's planar rows (Export_NKF_AEC.py:524-525: far end, near end; DFSMN-AEC: near end, far end)
@@ -356,7 +357,15 @@ class StreamingSession:
     On an NKF-AEC session the stream carries the echo canceller itself -- the per-bin Kalman state, the last 768 samples of the far-end and the near-end
     signal and the ISTFT overlap -- so the filter keeps the echo path it has learnt across pushes.  ``in_channels`` is then 2 (far end, near end), ``push`` takes
     ``(n_streams, 2, samples_per_push)`` (or ``push_aec(far, near)``), and ``delay`` is 768 samples: the outputs equal the reference's graph on the whole signal
-    in one call, 768 samples later.  ``delay`` is also the length of the flush; it is 256 for GTCRN."""
+    in one call, 768 samples later.  ``delay`` is also the length of the flush; it is 256 for GTCRN.
+
+    On a DFSMN-AEC session the stream carries both stages: the NKF back end's state as above, the near-end and ``temp_aec`` samples no mask frame has consumed yet,
+    every layer's ``dilation * (lorder - 1)`` frames of memory history, the second half of the last synthesised frame and the final samples not yet due.
+    ``in_channels`` is 2 in THIS family's order (near end, far end: the opposite of NKF-AEC; ``push_aec(far, near)`` stacks the two in the session's order
+    either way) and ``delay`` is 1344 samples (84 ms): the outputs equal the reference's unfolded graph on the whole signal in one call, 1344 samples later,
+    whatever the push size, bit for bit.  This family has no whole-call DC removal, so that holds for any input.  ``flush`` (1344 samples) ends the signal and
+    needs a length the reference's static export accepts: the hops pushed a multiple of 5.  A stream returns audio only, also when the manifest has
+    ``output_vad_result = 1``; folded and unfolded manifests stream alike (a stream does not use the window length)."""
 
     def __init__(self, session: InferenceSession, n_streams: int, frames_per_push: int):
         self._lib, self._session = session._lib, session
@@ -376,7 +385,8 @@ class StreamingSession:
 
     def push(self, pcm: np.ndarray, want_f32: bool = False):
         """int16 (n_streams, samples_per_push) -> int16 of the same shape (+ fp32 pre-PCM waveform).
-        NKF-AEC: int16 (n_streams, 2, samples_per_push), far end then near end -> int16 (n_streams, samples_per_push)."""
+        NKF-AEC: int16 (n_streams, 2, samples_per_push), far end then near end -> int16 (n_streams, samples_per_push).
+        DFSMN-AEC: the same shapes, near end then far end (the ABI's order for that family)."""
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         if pcm.shape != self._in_shape:
             raise ValueError(f"expected int16 {self._in_shape}, got {pcm.shape}")
@@ -387,13 +397,15 @@ class StreamingSession:
         return (out, f32) if want_f32 else out
 
     def push_aec(self, far: np.ndarray, near: np.ndarray, want_f32: bool = False):
-        """NKF-AEC: two int16 (n_streams, samples_per_push) arrays, the far-end reference and the near-end microphone -> the echo-cancelled push."""
+        """NKF-AEC, DFSMN-AEC: two int16 (n_streams, samples_per_push) arrays, the far-end reference and the near-end microphone -> the echo-cancelled push.
+        The two are stacked in the order of the session's family."""
         if self.in_channels != 2:
-            raise ValueError("push_aec needs a stream of an NKF-AEC session")
+            raise ValueError("push_aec needs a stream of an NKF-AEC or DFSMN-AEC session")
         far, near = np.asarray(far), np.asarray(near)
         if far.shape != self._out_shape or near.shape != self._out_shape:
             raise ValueError(f"expected two int16 {self._out_shape} arrays, got {far.shape} and {near.shape}")
-        return self.push(np.stack([far, near], axis=1), want_f32)
+        rows = [near, far] if getattr(self._session, "_aec_near_first", False) else [far, near]
+        return self.push(np.stack(rows, axis=1), want_f32)
 
     def push_device(self, d_in, d_out, d_f32=None, stream: Optional[int] = None) -> None:
         if tuple(d_in.shape) != self._in_shape or tuple(d_out.shape) != self._out_shape:
@@ -404,7 +416,7 @@ class StreamingSession:
 
     def flush(self, want_f32: bool = False):
         """End of the signal: the last hop, int16 (n_streams, 256).  ``concatenate(pushes + [flush])[:, 256:]`` is then exactly the one-shot
-        output of the whole signal.  ``reset()`` before pushing again.  In general the flush is ``delay`` samples long (768 for NKF-AEC)."""
+        output of the whole signal.  ``reset()`` before pushing again.  In general the flush is ``delay`` samples long (768 for NKF-AEC, 1344 for DFSMN-AEC)."""
         out = np.empty((self.n_streams, self.delay), np.int16)
         f32 = np.empty((self.n_streams, self.delay), np.float32) if want_f32 else None
         self._lib.check(self._lib.c.ade_stream_flush(self._h, out.ctypes.data, f32.ctypes.data if want_f32 else None), self._session._h)

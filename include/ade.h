@@ -177,7 +177,7 @@ ade_status ade_istft_forward(ade_handle h, const float* d_spec, int batch, int f
  * on the whole signal in one call (every op of the network is causal in time), with two stated differences: the output is one
  * hop (256 samples, 16 ms) behind the input -- a frame is complete one hop after its centre -- with the stream's first hop zero;
  * and the per-call DC removal of GTCRN_CUSTOM.forward (Export_GTCRN.py:647, a mean over the WHOLE call, not computable causally)
- * is not applied.  Plain GTCRN handles (not batch-fold; of the other model families NKF-AEC streams, see below).  All streams of a handle advance together.
+ * is not applied.  Plain GTCRN handles (not batch-fold; of the other model families NKF-AEC and DFSMN-AEC stream, see below).  All streams of a handle advance together.
  * A push of up to 512 frames is ONE kernel launch (the fused chunk kernel continuing from the state its previous launch left); longer pushes, or a
  * stream created while the option "fused" is 0, take the multi-kernel sequence. */
 typedef struct ade_stream* ade_stream_handle;
@@ -192,7 +192,7 @@ ade_status ade_stream_push_device(ade_stream_handle s, const int16_t* d_in, int1
 ade_status ade_stream_flush(ade_stream_handle s, int16_t* out_pcm, float* out_f32);
 ade_status ade_stream_reset(ade_stream_handle s);      /* back to a fresh stream (zero state, next push reflects its head) */
 void ade_stream_destroy(ade_stream_handle s);           /* before ade_destroy of its engine */
-/* Samples the stream's output lags its input, which is also the flush length per stream: 256 for a GTCRN stream, 768 for an NKF-AEC stream. */
+/* Samples the stream's output lags its input, which is also the flush length per stream: 256 for a GTCRN stream, 768 for an NKF-AEC stream, 1344 for a DFSMN-AEC stream. */
 ade_status ade_stream_delay(ade_stream_handle s, int* samples);
 
 /* ---- stateful streaming over the NKF-AEC path (model_family "nkf_aec"; the same entry points) -------------------------------
@@ -220,6 +220,40 @@ ade_status ade_stream_delay(ade_stream_handle s, int* samples);
  * transform holds one frame index only (the far-end and near-end frame of index t in the analysis, one frame in the synthesis).
  * Scope: int16 PCM in and out at 16 kHz; a handle with float audio tensors or another output rate answers ADE_ERR_UNSUPPORTED.
  * ade_stream_push_device enqueues four kernels on the caller's stream and does not synchronise. */
+
+/* ---- stateful streaming over the DFSMN-AEC path (model_family "dfsmn_aec"; the same entry points) ----------------------------
+ * The one-shot call, and every folded 1.5 s window of it, restarts the Kalman filter of the NKF back end and zeroes the memory of the
+ * mask network.  A stream carries both stages.  Every operation of the second stage is causal and frame-local (DFSMN_AEC.forward,
+ * Export_DFSMN_AEC.py:1268-1352: the Kaldi frames remove a per-frame mean, the depthwise memory is causal, the 640 / 320 mask STFT
+ * has no centre pad) and this family has no whole-call DC removal, so for ANY input pushes plus the flush equal the reference's
+ * unfolded graph on the whole signal in ONE call, 1344 samples later, within the family's gates (waveform 1e-4, PCM 1 LSB).
+ * Eligible handles: int16 audio at 16 kHz on both sides (F32 / F16 audio tensors or another sample rate: ADE_ERR_UNSUPPORTED, the
+ * message names int16 / 16000); a folded or an unfolded manifest (a stream does not use the window length); either ade_dft_tables
+ * mode, which the stream follows (reference: the back end's transforms are dense products with the reference's tables; exact: its
+ * FFT stream kernels).  A handle with output_vad_result = 1 is accepted; a stream returns AUDIO ONLY.
+ * Buffers: in [n_streams][2][frames_per_push * 256] int16, channel 0 the NEAR end, channel 1 the FAR end (this family's order in
+ * ade_process, the opposite of nkf_aec); out [n_streams][frames_per_push * 256] int16, out_f32 optional float of the same shape (the
+ * waveform before the PCM tail).  1 <= frames_per_push <= 4096.  All streams of a handle advance together.  ade_stream_push_device
+ * enqueues on the caller's stream and does not synchronise.
+ * Delay: 1344 samples (84 ms), the minimum, and exact.  After k hops of input
+ *   - the back end (768 samples behind, see above) has nt = 256 max(0, k - 3) final temp_aec samples;
+ *   - mask frame m needs temp_aec and near-end samples [320 m, 320 m + 640), so M = 0 frames are complete if nt < 640, else
+ *     M = (nt - 640) / 320 + 1 (integer division);
+ *   - an output sample is final once both frames that cover it are complete: 320 M samples;
+ *   - nt - 640 - 320 (M - 1) <= 319 and is a multiple of 64 (gcd(256, 320)), hence <= 256, so 320 M >= nt - 576 = 256 k - 1344, with
+ *     equality at k = 9, 14, 19, ...: a push of F hops can always emit its 256 F samples at a lag of 1344, and at no smaller lag.
+ *     (Also checked by enumeration for k < 4000.)  At most 256 final samples wait for the next push.
+ * The stream's first 1344 output samples are zero; output sample j of the stream is sample j - 1344 of the one-call result.  A push
+ * that completes no mask frame (with one-hop pushes every fifth) runs the back end only and still emits its samples.
+ * ade_stream_flush returns the last 1344 samples per stream (out [n_streams][1344]) and ends the signal of L = 256 K samples after
+ * K hops: the back end's last two frames, the remaining three mask frames, the end-of-signal entries of the static window-square
+ * table.  Signal indices below zero come out as zeros (K = 5 only).  It is defined only where the reference's static export accepts
+ * the length, L % 320 == 0: K a multiple of 5, at least 5; otherwise ADE_ERR_BAD_VALUE with a message that says so (the stream
+ * stays usable).  After a flush the stream must be reset before it is pushed again.
+ * The result does not depend on frames_per_push, bit for bit, PCM and f32: every transform holds one frame (the mask synthesis runs
+ * one frame per FFT; the one-shot kernel's pairs would make a frame's rounding depend on where the push ends), the memory sums its
+ * taps in the one-shot order from a per-layer history of dilation * (lorder - 1) frames, and the overlap-add adds at most two frames
+ * in ascending order and reads the one-shot's 1 / window-square table. */
 
 /* ---- generic STFT_Process operator: any n_fft / win_length / hop / window, for the other model families -------
  * Replaces the reference's STFT_Process module in its 'stft_B' (packed) and 'istft_B' (packed, static_norm=True) forms

@@ -15,6 +15,8 @@ What stands in for the parts the container lacks:
     ``weightgen.NKF_GAIN_LAYER_SCALE`` (the stability rule of tools/make_golden_nkf_aec.py).
 
     python tools/make_golden_dfsmn_aec.py      # writes tests/golden/dfsmn_aec_seed0.adew and dfsmn_aec_seed0_*.npz
+    python tools/make_golden_dfsmn_aec.py --stream        # writes tests/golden/dfsmn_aec_seed0_stream.npz only: the unfolded forward in ONE call on two clips of
+                                                          # 40 960 samples, what ade_stream_* pushes + flush must equal 1344 samples later
     python tools/make_golden_dfsmn_aec.py --geometry      # writes tests/golden/aec_geom_<name>.npz only: the geometries of tests/aec_geometry_lib.py, whose
                                                           # generated weights (per-layer H / lorder / dilation / skip, distinct PReLU slopes) replace the stand-ins
 """
@@ -415,6 +417,34 @@ def main(seed=0):
             print(fn_, os.path.getsize(os.path.join(GOLD, fn_)))
 
 
+STREAM_LEN, STREAM_OFFSETS = 40960, (20000, 80000)      # 160 hops, 127 mask frames; two cuts of the reference's example recordings
+
+
+def stream_fixture(seed=0):
+    """tests/golden/dfsmn_aec_seed0_stream.npz: the reference's unfolded DFSMN_AEC.forward in ONE call on two clips of 40 960 samples, with the committed
+    seed-0 state (the construction is seeded; the state it yields is checked against tests/golden/dfsmn_aec_seed0_state.npz).  int16 near / far / out and the
+    f32 waveform before the PCM tail, per clip."""
+    far_all, near_all = rows()
+    ns = import_namespace(USE_BATCH_FOLD=False, INPUT_AUDIO_LENGTH=STREAM_LEN)
+    assert ns["MODEL_BATCH"] == 1 and ns["MASK_FRAMES_A2"] == 127 and ns["BACKEND_FRAMES_B"] == 161
+    model, nkf_state, dfsmn_state = build(ns, seed)
+    committed = np.load(os.path.join(GOLD, f"dfsmn_aec_seed{seed}_state.npz"))
+    for prefix, state in (("nkf/", nkf_state), ("dfsmn/", dfsmn_state)):
+        for k, v in state.items():
+            assert np.array_equal(committed[prefix + k], v), prefix + k
+    out = {}
+    for i, o in enumerate(STREAM_OFFSETS):
+        near, far = np.ascontiguousarray(near_all[o:o + STREAM_LEN]), np.ascontiguousarray(far_all[o:o + STREAM_LEN])
+        assert near.shape == far.shape == (STREAM_LEN,)
+        pcm, _, taps = run(ns, model, near, far, taps=True)
+        out[f"near{i}"], out[f"far{i}"], out[f"out{i}"], out[f"wave{i}"] = near, far, pcm.astype(np.int16), taps["wave"].reshape(-1).astype(np.float32)
+        print(f"clip {i}: rms near {np.sqrt(np.mean((near / 32768.0) ** 2)):.4f} out {np.sqrt(np.mean((pcm / 32767.0) ** 2)):.4f}")
+    path = os.path.join(GOLD, f"dfsmn_aec_seed{seed}_stream.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < (1 << 20)
+
+
 def geometry_fixtures():
     """tests/golden/aec_geom_<name>.npz for every geometry of tests/aec_geometry_lib.py: the reference's DFSMN_AEC.forward (unfolded 3200, every row; folded
     2 x 1600, two calls) and NKF.forward (3200 and 3000 samples) on the generated weights, and the recorded distances the tests' gates are read from."""
@@ -509,5 +539,7 @@ def geometry_fixtures():
 if __name__ == "__main__":
     if "--geometry" in sys.argv:
         geometry_fixtures()
+    elif "--stream" in sys.argv:
+        stream_fixture()
     else:
         main()
