@@ -57,7 +57,7 @@ EXPORTED_SYMBOLS = (
     "ade_kernel_count", "ade_kernel_name", "ade_profile_last", "ade_kernel_ms", "ade_last_error", "ade_destroy",
     "ade_stft_forward", "ade_istft_forward",
     "ade_stft_create", "ade_stft_frames", "ade_stft_output_length", "ade_stft_keep_tail", "ade_stft_analyze", "ade_stft_synthesize", "ade_stft_synthesize_polar",
-    "ade_stream_create", "ade_stream_push", "ade_stream_push_device", "ade_stream_flush", "ade_stream_reset", "ade_stream_destroy", "ade_stream_delay",
+    "ade_stream_create", "ade_stream_push", "ade_stream_push_device", "ade_stream_flush", "ade_stream_reset", "ade_stream_destroy", "ade_stream_delay", "ade_stream_hop",
     "ade_stft_last_error", "ade_stft_destroy",
 )
 
@@ -92,6 +92,7 @@ class AdeLibrary:
         L.ade_stream_destroy.argtypes = [C.c_void_p]
         L.ade_stream_destroy.restype = None
         L.ade_stream_delay.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.ade_stream_hop.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.ade_process.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.ade_process_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ade_submit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]

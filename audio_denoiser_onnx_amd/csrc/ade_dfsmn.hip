@@ -16,6 +16,14 @@
 //   layers     X(256, N)  = relu(W x + b) ...                            store = bias + ReLU / none ; the last one bias + sigmoid, transposed to (N, 961)
 //   synthesis  frames(N, 1920) = hamming_periodic * Re IFFT_1920(hermitian(mask * S))                                                   k_dfsmn_synthesis
 // followed by a gather overlap-add with the PCM tail fused.  Twiddles are exact (double-precision angles), like the dense tables they replace.
+//
+// Streams (ade_stream_* on a dfsmn handle, include/ade.h): the model is causal from end to end -- per-frame Kaldi mean, no centre
+// pad, a memory that looks lorder - 1 frames back -- so a push of F hops (960 samples each) continues the signal, one hop behind the input:
+//   k_dfsmn_stream_analysis   rows [960 carried | 960 F new]; ONE frame per transform, each real transform as a half-length complex FFT plus a split pass
+//   mask network              the same GEMMs, N = streams x the frames the push completes
+//   k_dfsmn_stream_memory     the memory with the frames before the push taken from the layer's history, which it also renews
+//   k_dfsmn_stream_synthesis  the Hermitian inverse of one frame as a 960-point complex transform
+//   k_dfsmn_stream_out        two-frame overlap-add from the carried half frame, / the window-square sum, the PCM tail, the next carried half
 #include "ade_fft.h"
 #include "ade_gemm.h"
 #include "ade_internal.h"
@@ -23,6 +31,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 
 namespace ade {
 
@@ -179,6 +188,151 @@ __global__ __launch_bounds__(256) void k_dfsmn_ola_pcm(const float* __restrict__
     if (pcm) pcm[i] = (short)(int)fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f);
 }
 
+// ---- streams ----------------------------------------------------------------------------------------------------------------------------------------------------
+constexpr int kHalfK = kKaldiNfft / 2, kHalfS = kNfftD / 2;      // 1024, 960: the complex lengths of the two real transforms
+
+// A real transform of n = 2 h samples from the h-point complex FFT Z of z[m] = x[2 m] + i x[2 m + 1]:  X[f] = E[f] + w_n^f O[f],  f <= h, with
+// E[f] = (Z[f] + conj Z[h - f]) / 2 (the even samples' transform) and O[f] = (Z[f] - conj Z[h - f]) / (2 i) (the odd samples'); Z[h] = Z[0].
+__device__ __forceinline__ float2 split_bin(const float2* __restrict__ r, int f, int h, const float2* __restrict__ tw) {
+    const float2 z = r[f == h ? 0 : f], zc = r[f == 0 ? 0 : h - f];
+    const float2 e = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y)), o = make_float2(0.5f * (z.y + zc.y), 0.5f * (zc.x - z.x));
+    return fft::cadd(e, fft::cmul(tw[f], o));
+}
+
+// One workgroup per frame the push completes, plus one per stream that renews the carried input.  A stream's row is [960 carried samples | the push's 960 F samples];
+// completed frame i of stream s (column s * Mp + i) covers row samples [off + 960 i, off + 960 i + 1920): off = 0, or 960 on a fresh stream, whose carried samples are
+// no signal.  ONE frame per transform: k_dfsmn_analysis rides two frames on one complex FFT and the partner's rounding leaks into a frame, which would make a frame's
+// bits depend on where a push ends.  Each real transform is instead a half-length complex one (2048 real -> 1024 complex, 1920 real -> 960 complex: even samples the
+// real part, odd the imaginary) and a split pass; the butterflies per frame stay what the paired kernel spends, the LDS per workgroup halves.
+// The Kaldi branch keeps k_dfsmn_analysis's order: mean in double, subtract, 0.97 pre-emphasis, symmetric hamming, zero pad.
+__global__ __launch_bounds__(256) void k_dfsmn_stream_analysis(const int16_t* __restrict__ in, const int16_t* __restrict__ carry_in, int16_t* __restrict__ carry_out, int P, int Mp, int N,
+                                                               int off, fft::Plan p1024, fft::Plan p960, const float2* __restrict__ tw1024, const float2* __restrict__ tw960,
+                                                               const float2* __restrict__ tw2048, const float2* __restrict__ tw1920, const float* __restrict__ win_fb,
+                                                               const float* __restrict__ win_st, float* __restrict__ power, float* __restrict__ spec) {
+    __shared__ float2 A[kHalfK];
+    __shared__ float2 B[kHalfK];
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= N) {                   // the row's last 960 samples (always of this push: F >= 1) are what the next push's first frame starts with
+        const int s = (int)blockIdx.x - N;
+        for (int n = tid; n < kHopD; n += 256) carry_out[(size_t)s * kHopD + n] = in[(size_t)s * P + (P - kHopD) + n];
+        return;
+    }
+    const int fr = (int)blockIdx.x, s = fr / Mp, i = fr - s * Mp, r0 = off + i * kHopD;
+    const int16_t *old = carry_in + (size_t)s * kHopD, *row = in + (size_t)s * P;               // row position r: old[r] below 960, row[r - 960] from there on
+    auto sample = [&](int n) { const int r = r0 + n; return (float)(r < kHopD ? old[r] : row[r - kHopD]) * (1.0f / 32768.0f); };
+    double part = 0.0;
+    for (int n = tid; n < kFrame; n += 256) part += (double)sample(n);
+    red[tid] = part;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    const float mean = (float)(red[0] / (double)kFrame);
+    for (int m = tid; m < kHalfK; m += 256) {
+        float v[2] = {0.0f, 0.0f};
+        if (2 * m < kFrame) {
+            const float yp = sample(m > 0 ? 2 * m - 1 : 0) - mean, y0 = sample(2 * m) - mean, y1 = sample(2 * m + 1) - mean;
+            v[0] = (y0 - 0.97f * yp) * win_fb[2 * m];
+            v[1] = (y1 - 0.97f * y0) * win_fb[2 * m + 1];
+        }
+        A[m] = make_float2(v[0], v[1]);
+    }
+    float2* r = fft::forward(A, B, p1024, tw1024, tid, 256);
+    for (int f = tid; f < kFbBins; f += 256) {
+        const float2 x = split_bin(r, f, kHalfK, tw2048);
+        power[(size_t)fr * kFbBins + f] = (x.x * x.x + x.y * x.y) * (32768.0f * 32768.0f);
+    }
+    __syncthreads();
+    for (int m = tid; m < kHalfS; m += 256) A[m] = make_float2(sample(2 * m) * win_st[2 * m], sample(2 * m + 1) * win_st[2 * m + 1]);
+    r = fft::forward(A, B, p960, tw960, tid, 256);
+    for (int f = tid; f < kStBins; f += 256) {
+        const float2 x = split_bin(r, f, kHalfS, tw1920);
+        spec[(size_t)fr * 2 * kStBins + f] = x.x;
+        spec[(size_t)fr * 2 * kStBins + kStBins + f] = x.y;
+    }
+}
+
+// k_fsmn_memory over the Mp frames a push completes, column j = stream * Mp + i.  A tap that reaches before the push reads the layer's history, hist_in [c][stream][Hl]:
+// the Hl = lo - 1 frames of p1 before the push, oldest first, zeros before the stream's first frame (the reset's memset).  The taps are summed in k_fsmn_memory's
+// order.  The threads from `total` on write the next history into hist_out: the last Hl frames of [history | push].
+__global__ __launch_bounds__(256) void k_dfsmn_stream_memory(const float* __restrict__ p1, const float* __restrict__ w, float* __restrict__ x, const float* __restrict__ hist_in,
+                                                             float* __restrict__ hist_out, int S, int Mp, int Hl, int lo, long long total, long long total_all) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total_all) return;
+    const int N = S * Mp;
+    if (i < total) {
+        const int c = (int)(i / N), j = (int)(i - (long long)c * N), st = j / Mp, t = j - st * Mp;
+        const float* row = p1 + (size_t)c * N + j;
+        const float* old = hist_in + ((size_t)c * S + st) * Hl + Hl + t;          // old[dt]: frame t + dt of the push, t + dt < 0
+        float s = 0.0f;
+        for (int k = 0; k < lo; ++k) {
+            const int dt = k - (lo - 1);
+            const float v = t + dt >= 0 ? row[dt] : old[dt];
+            s += w[c * lo + k] * v;
+        }
+        x[i] += s;
+        return;
+    }
+    const long long e = i - total;                                                // (c, stream, slot): slot q holds frame Mp - Hl + q of the push
+    const int q = (int)(e % Hl), cs = (int)(e / Hl), c = cs / S, st = cs - c * S, t = Mp - Hl + q;
+    hist_out[e] = t >= 0 ? p1[(size_t)c * N + (size_t)st * Mp + t] : hist_in[(size_t)cs * Hl + (Hl + t)];
+}
+
+// One workgroup per frame: mask * spectrum (:236-237) -> the Hermitian inverse 1920-point transform of ONE frame as a 960-point complex one -> * periodic hamming / N.
+// With X the masked half spectrum (imaginary parts of the DC and Nyquist bins zero, as in k_dfsmn_synthesis) and h = 960:
+//   W[f] = (X[f] + conj X[h - f]) + i (X[f] - conj X[h - f]) e^{+2 pi i f / N},  f < h;   x[2 m] + i x[2 m + 1] = (1 / N) sum_f W[f] e^{+2 pi i f m / h} = conj(DFT_h(conj W))[m] / N
+__global__ __launch_bounds__(256) void k_dfsmn_stream_synthesis(const float* __restrict__ spec, const float* __restrict__ mask, fft::Plan p960, const float2* __restrict__ tw960,
+                                                                const float2* __restrict__ tw1920, const float* __restrict__ win_syn, float* __restrict__ frames) {
+    __shared__ float2 A[kHalfS];
+    __shared__ float2 B[kHalfS];
+    const int tid = threadIdx.x, fr = (int)blockIdx.x;
+    const float *sp = spec + (size_t)fr * 2 * kStBins, *mk = mask + (size_t)fr * kStBins;
+    auto bin = [&](int f) { const float m = mk[f]; return make_float2(sp[f] * m, f == 0 || f == kStBins - 1 ? 0.0f : sp[kStBins + f] * m); };
+    for (int f = tid; f < kHalfS; f += 256) {
+        const float2 a = bin(f), b = bin(kHalfS - f), t = tw1920[f];          // conj X[h - f] = (b.x, -b.y); e^{+2 pi i f / N} = conj t
+        const float2 sm = make_float2(a.x + b.x, a.y - b.y), d = make_float2(a.x - b.x, a.y + b.y);
+        const float2 dt = make_float2(d.x * t.x + d.y * t.y, d.y * t.x - d.x * t.y);
+        A[f] = make_float2(sm.x - dt.y, -(sm.y + dt.x));                        // conj(sm + i dt)
+    }
+    const float2* r = fft::forward(A, B, p960, tw960, tid, 256);
+    float2* out = reinterpret_cast<float2*>(frames + (size_t)fr * kNfftD);
+    for (int m = tid; m < kHalfS; m += 256)
+        out[m] = make_float2((r[m].x * (1.0f / (float)kNfftD)) * win_syn[2 * m], (-r[m].y * (1.0f / (float)kNfftD)) * win_syn[2 * m + 1]);
+}
+
+// Output of a push (or of the flush) and the next carried half frame.  Output hop k of stream s is the second half of the frame before local frame i = k - lead plus the
+// first half of frame i, added in ascending frame order as k_dfsmn_ola_pcm does, over the matching sum of squared windows wsq [head | steady | tail][960]:
+//   i < 0           the delay hop of a fresh stream (lead = 1): zero
+//   i == 0          the frame before is the carried half (has_prev), or there is none: the signal's first hop, first-half term and the head sum only
+//   i == Mp         the flush (Mp = 0, has_prev): the second-half term and the tail sum only
+// The threads from `total` on copy the second half of the push's last frame into half_out [stream][960] (none when Mp = 0).
+__global__ __launch_bounds__(256) void k_dfsmn_stream_out(const float* __restrict__ frames, const float* __restrict__ half_in, float* __restrict__ half_out,
+                                                          const float* __restrict__ wsq, int Mp, int Pout, int lead, int has_prev, int16_t* __restrict__ pcm,
+                                                          float* __restrict__ f32, long long total, long long total_all) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= total_all) return;
+    if (g >= total) {
+        const long long e = g - total;
+        const int st = (int)(e / kHopD), n = (int)(e - (long long)st * kHopD);
+        half_out[e] = frames[((size_t)st * Mp + (Mp - 1)) * kNfftD + kHopD + n];
+        return;
+    }
+    const int st = (int)(g / Pout), q = (int)(g - (long long)st * Pout), k = q / kHopD, n = q - k * kHopD, i = k - lead;
+    float y = 0.0f;
+    if (i >= 0) {
+        float s = 0.0f;
+        const bool prev = i > 0 || has_prev, cur = i < Mp;
+        if (i > 0) s += frames[((size_t)st * Mp + i - 1) * kNfftD + kHopD + n];
+        else if (has_prev) s += half_in[(size_t)st * kHopD + n];
+        if (cur) s += frames[((size_t)st * Mp + i) * kNfftD + n];
+        y = s / wsq[(prev ? (cur ? kHopD : 2 * kHopD) : 0) + n];
+    }
+    if (f32) f32[g] = y;
+    if (pcm) pcm[g] = (short)(int)fminf(fmaxf(y * 32768.0f, -32768.0f), 32767.0f);
+}
+
 void hamming(int n, bool periodic, std::vector<double>& w) {   // torch.hamming_window(alpha 0.54, beta 0.46)
     w.resize((size_t)n);
     const double denom = periodic ? n : n - 1;
@@ -197,8 +351,9 @@ struct DfsmnEngine : SubEngine {
     float* d_w = nullptr;      // one arena: tables + weights
     const float *win_fb = nullptr, *win_st = nullptr, *win_syn = nullptr, *wsum = nullptr, *mel = nullptr, *lin1_w = nullptr, *lin1_b = nullptr, *lin2_w = nullptr,
                 *lin2_b = nullptr;
-    const float2 *tw2048 = nullptr, *tw1920 = nullptr;
-    fft::Plan p2048, p1920;
+    const float2 *tw2048 = nullptr, *tw1920 = nullptr, *tw1024 = nullptr, *tw960 = nullptr;      // (the half-length tables and plans: streams)
+    const float* wsq = nullptr;     // [3][960] sum of squared synthesis windows over a hop: the signal's first hop | two frames | its last hop (streams)
+    fft::Plan p2048, p1920, p1024, p960;
     std::vector<const float*> uf_lin_w, uf_lin_b, uf_proj_w, uf_conv_w;
     int capacity = 0;
     float* ws = nullptr;
@@ -217,6 +372,29 @@ struct DfsmnEngine : SubEngine {
     int reserve(int batch, std::string& err) override;
     int run(hipStream_t s, const int16_t* d_in, int batch, int16_t* d_out, float* d_f32, std::string& err) override;
     int tap(hipStream_t s, const char* name, int batch, float* out, size_t count, size_t* written, std::string& err) override;
+    // streams (ade_stream_*): state per stream object, see DfsmnStream below
+    int stream_delay() const override { return kHopD; }
+    int stream_hop() const override { return kHopD; }
+    int stream_windows() const override { return n_win; }
+    int stream_channels() const override { return 1; }
+    int stream_create(int n_streams, int frames_per_push, void** state, std::string& err) override;
+    int stream_reset(void* state, hipStream_t s, std::string& err) override;
+    int stream_push(void* state, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) override;
+    int stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) override;
+    void stream_destroy(void* state) override;
+};
+
+// What a stream carries between pushes, for S streams that advance together: one allocation, its leading part cleared by a reset.
+struct DfsmnStream {
+    int S = 0, F = 0;                           // streams, hops per push
+    long long hops = 0;                         // hops pushed since the last reset
+    int16_t* carry[2] = {};                     // [S][960] the last 960 input samples, ping-ponged every push (ccur)
+    float* hist[2] = {};                        // per layer [256][S][lorder - 1]: the last frames of the projection output p1, ping-ponged with half (cur)
+    float* half[2] = {};                        // [S][960] the second half of the last synthesised frame
+    int ccur = 0, cur = 0;
+    float *power = nullptr, *spec = nullptr, *feat = nullptr, *x = nullptr, *f1 = nullptr, *p1 = nullptr, *mask = nullptr, *frames = nullptr;     // one push's workspace, S * F frames
+    void* block = nullptr;
+    size_t reset_bytes = 0;
 };
 
 namespace {
@@ -283,8 +461,18 @@ int dfsmn_create(const std::map<std::string, Tensor>& tensors, int in_len, int n
         for (int m = 0; m < n; ++m) { const double a = -2.0 * M_PI * (double)m / (double)n; tw[2 * m] = (float)cos(a); tw[2 * m + 1] = (float)sin(a); }
         return push(tw.data(), tw.size());
     };
-    const size_t o_tw2048 = twiddles(kKaldiNfft), o_tw1920 = twiddles(kNfftD);
-    if (!fft::make_plan(kKaldiNfft, &d->p2048) || !fft::make_plan(kNfftD, &d->p1920)) { delete d; return dfail(err, ADE_ERR_UNSUPPORTED, "dfsmn: FFT plan"); }
+    const size_t o_tw2048 = twiddles(kKaldiNfft), o_tw1920 = twiddles(kNfftD), o_tw1024 = twiddles(kHalfK), o_tw960 = twiddles(kHalfS);
+    if (!fft::make_plan(kKaldiNfft, &d->p2048) || !fft::make_plan(kNfftD, &d->p1920) || !fft::make_plan(kHalfK, &d->p1024) || !fft::make_plan(kHalfS, &d->p960)) {
+        delete d;
+        return dfail(err, ADE_ERR_UNSUPPORTED, "dfsmn: FFT plan");
+    }
+    const size_t o_wsq = push(nullptr, (size_t)3 * kHopD);        // summed like the static table below: frame t - 1's second half first, then frame t's first half
+    for (int n = 0; n < kHopD; ++n) {
+        const float lo2 = wsyn[n] * wsyn[n], hi2 = wsyn[kHopD + n] * wsyn[kHopD + n];
+        arena[o_wsq + n] = 0.0f + lo2;
+        arena[o_wsq + kHopD + n] = (0.0f + hi2) + lo2;
+        arena[o_wsq + 2 * kHopD + n] = 0.0f + hi2;
+    }
     const size_t o_ws = push(nullptr, (size_t)d->out_len_);
     for (int t = 0; t < d->T; ++t)
         for (int n = 0; n < kNfftD; ++n) arena[o_ws + (size_t)t * kHopD + n] += wsyn[n] * wsyn[n];
@@ -304,6 +492,7 @@ int dfsmn_create(const std::map<std::string, Tensor>& tensors, int in_len, int n
         return bail(dfail(err, ADE_ERR_DEVICE, "upload of the DFSMN weights failed"));
     d->win_fb = d->d_w + o_wfb; d->win_st = d->d_w + o_wst; d->win_syn = d->d_w + o_wsyn; d->wsum = d->d_w + o_ws; d->mel = d->d_w + o_mel;
     d->tw2048 = reinterpret_cast<const float2*>(d->d_w + o_tw2048); d->tw1920 = reinterpret_cast<const float2*>(d->d_w + o_tw1920);
+    d->tw1024 = reinterpret_cast<const float2*>(d->d_w + o_tw1024); d->tw960 = reinterpret_cast<const float2*>(d->d_w + o_tw960); d->wsq = d->d_w + o_wsq;
     d->lin1_w = d->d_w + o_l1w; d->lin1_b = d->d_w + o_l1b; d->lin2_w = d->d_w + o_l2w; d->lin2_b = d->d_w + o_l2b;
     for (int i = 0; i < depth; ++i) {
         d->uf_lin_w.push_back(d->d_w + o_h[4 * i]);
@@ -383,6 +572,106 @@ int DfsmnEngine::tap(hipStream_t s, const char* name, int batch, float* out, siz
     DF_HIP(hipMemcpy(out, src, n * sizeof(float), hipMemcpyDeviceToHost));
     *written = n;
     return ADE_OK;
+}
+
+// ---- streams ----------------------------------------------------------------------------------------------------------------------------------------------------
+int DfsmnEngine::stream_create(int n_streams, int frames_per_push, void** state, std::string& err) {
+    *state = nullptr;
+    if (n_streams < 1 || frames_per_push < 1 || frames_per_push > 4096)
+        return dfail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: dfsmn needs n_streams >= 1 and 1 <= frames_per_push <= 4096");
+    const size_t S = (size_t)n_streams, N = S * frames_per_push, Hl = (size_t)(lorder - 1);
+    if (N * kNfftD > 0x7fffffffULL || (size_t)kHid * S * (Hl > (size_t)frames_per_push ? Hl : (size_t)frames_per_push) > 0x7fffffffULL)
+        return dfail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: dfsmn: n_streams * frames_per_push exceeds the launch grid");
+    std::unique_ptr<DfsmnStream> st(new DfsmnStream());
+    st->S = n_streams; st->F = frames_per_push;
+    auto up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t b_carry = up(S * kHopD * sizeof(int16_t)), b_hist = up((size_t)depth * kHid * S * Hl * sizeof(float)), b_half = up(S * kHopD * sizeof(float));
+    const size_t work[8] = {up(N * kFbBins * sizeof(float)), up(N * 2 * kStBins * sizeof(float)), up(N * kMel * sizeof(float)), up(N * kHid * sizeof(float)),
+                            up(N * kHid * sizeof(float)), up(N * kHid * sizeof(float)), up(N * kStBins * sizeof(float)), up(N * kNfftD * sizeof(float))};
+    size_t total = 2 * b_carry + 2 * b_hist + 2 * b_half;
+    st->reset_bytes = total;
+    for (size_t b : work) total += b;
+    if (hipSetDevice(device) != hipSuccess || hipMalloc(&st->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        return dfail(err, ADE_ERR_DEVICE, "ade_stream_create: hipMalloc of the DFSMN stream state failed");
+    }
+    char* p = (char*)st->block;
+    for (int i = 0; i < 2; ++i) { st->carry[i] = (int16_t*)p; p += b_carry; }
+    for (int i = 0; i < 2; ++i) { st->hist[i] = (float*)p; p += b_hist; }
+    for (int i = 0; i < 2; ++i) { st->half[i] = (float*)p; p += b_half; }
+    float** ptrs[8] = {&st->power, &st->spec, &st->feat, &st->x, &st->f1, &st->p1, &st->mask, &st->frames};
+    for (int i = 0; i < 8; ++i) { *ptrs[i] = (float*)p; p += work[i]; }
+    *state = st.release();
+    return ADE_OK;
+}
+
+int DfsmnEngine::stream_reset(void* state, hipStream_t s, std::string& err) {
+    DfsmnStream* st = (DfsmnStream*)state;
+    DF_HIP(hipMemsetAsync(st->block, 0, st->reset_bytes, s));
+    st->hops = 0;
+    st->ccur = 0;
+    st->cur = 0;
+    return ADE_OK;
+}
+
+// A push of F hops.  A fresh stream's first push completes F - 1 frames (its carried samples are no signal), every later push F.
+int DfsmnEngine::stream_push(void* state, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) {
+    using namespace gemm;
+    DfsmnStream* st = (DfsmnStream*)state;
+    const bool fresh = st->hops == 0;
+    const int S = st->S, P = st->F * kHopD, Mp = fresh ? st->F - 1 : st->F, N = S * Mp, Hl = lorder - 1;
+    const int nxt = st->cur ^ 1;
+    // 1. analysis of the frames this push completes (none: a one-hop first push), and the next carried input -- N + S >= 1 workgroups
+    hipLaunchKernelGGL(k_dfsmn_stream_analysis, dim3((unsigned)(N + S)), dim3(256), 0, s, d_in, (const int16_t*)st->carry[st->ccur], st->carry[st->ccur ^ 1], P, Mp, N,
+                       fresh ? kHopD : 0, p1024, p960, tw1024, tw960, tw2048, tw1920, win_fb, win_st, st->power, st->spec);
+    if (Mp > 0) {
+        // 2. Kaldi log-mel and the mask network, the memory continued from each layer's history
+        launch(s, RowMajorA{mel, kFbBins}, PowerFrameB{st->power}, BiasActStore<kActLogFloor>{st->feat, N, nullptr, 1.1920928955078125e-07f}, kMel, N, kFbBins);
+        launch(s, RowMajorA{lin1_w, kMel}, RowMajorB{st->feat, N}, BiasActStore<kActRelu>{st->x, N, lin1_b, 0.0f}, kHid, N, kMel);
+        for (int i = 0; i < depth; ++i) {
+            launch(s, RowMajorA{uf_lin_w[i], kHid}, RowMajorB{st->x, N}, BiasActStore<kActRelu>{st->f1, N, uf_lin_b[i], 0.0f}, kHid, N, kHid);
+            launch(s, RowMajorA{uf_proj_w[i], kHid}, RowMajorB{st->f1, N}, BiasActStore<kActNone>{st->p1, N, nullptr, 0.0f}, kHid, N, kHid);
+            const size_t at = (size_t)i * kHid * S * Hl;
+            const long long total = (long long)kHid * N, total_all = total + (long long)kHid * S * Hl;
+            hipLaunchKernelGGL(k_dfsmn_stream_memory, dim3((unsigned)((total_all + 255) / 256)), dim3(256), 0, s, (const float*)st->p1, uf_conv_w[i], st->x,
+                               (const float*)(st->hist[st->cur] + at), st->hist[nxt] + at, S, Mp, Hl, lorder, total, total_all);
+        }
+        launch(s, RowMajorA{lin2_w, kHid}, RowMajorB{st->x, N}, SigmoidTStore{st->mask, lin2_b}, kStBins, N, kHid);
+        // 3. one inverse transform per frame
+        hipLaunchKernelGGL(k_dfsmn_stream_synthesis, dim3((unsigned)N), dim3(256), 0, s, (const float*)st->spec, (const float*)st->mask, p960, tw960, tw1920, win_syn, st->frames);
+    }
+    // 4. overlap-add, window-square sum, PCM tail, the next carried half
+    {
+        const long long total = (long long)S * P, total_all = total + (Mp > 0 ? (long long)S * kHopD : 0);
+        hipLaunchKernelGGL(k_dfsmn_stream_out, dim3((unsigned)((total_all + 255) / 256)), dim3(256), 0, s, (const float*)st->frames, (const float*)st->half[st->cur], st->half[nxt],
+                           wsq, Mp, P, fresh ? 1 : 0, st->hops >= 2 ? 1 : 0, d_out, d_f32, total, total_all);
+    }
+    DF_HIP(hipGetLastError());
+    if (Mp > 0) st->cur = nxt;
+    st->ccur ^= 1;
+    st->hops += st->F;
+    return ADE_OK;
+}
+
+// The last hop: the second half of the last frame over its own window squares.  It ends a signal of 960 K samples, K >= 2 (one frame at least).
+int DfsmnEngine::stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) {
+    DfsmnStream* st = (DfsmnStream*)state;
+    if (st->hops < 2)
+        return dfail(err, ADE_ERR_BAD_VALUE, "ade_stream_flush: dfsmn ends a signal of at least one 1920-sample frame: the hops pushed must be at least 2 (pushed: " +
+                                             std::to_string(st->hops) + ")");
+    const long long total = (long long)st->S * kHopD;
+    hipLaunchKernelGGL(k_dfsmn_stream_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)st->frames, (const float*)st->half[st->cur], (float*)nullptr, wsq, 0,
+                       kHopD, 0, 1, d_out, d_f32, total, total);
+    DF_HIP(hipGetLastError());
+    return ADE_OK;
+}
+
+void DfsmnEngine::stream_destroy(void* state) {
+    DfsmnStream* st = (DfsmnStream*)state;
+    if (!st) return;
+    (void)hipSetDevice(device);
+    if (st->block) (void)hipFree(st->block);
+    delete st;
 }
 
 }  // namespace ade

@@ -918,6 +918,7 @@ struct ade_stream {
     // a sub-engine's stream (SubEngine::stream_*): the state is the sub-engine's, this object keeps the handle, the flags above and the host staging below
     void* sub_state = nullptr;
     int in_ch = 1, delay = kHop;     // PCM rows per stream and push; samples the output lags the input (= the flush length)
+    int hop = kHop;                  // samples of one hop: a push is N hops (SubEngine::stream_hop; 960 for a dfsmn stream)
     int16_t *pcm_prev = nullptr, *pcm_hist = nullptr, *concat = nullptr, *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
     float *d_f32 = nullptr, *h_f32 = nullptr;
     float* state = nullptr;      // one allocation: dc | conv histories (ping-pong) | TRA hidden | inter-GRU hidden | OLA carry
@@ -2282,9 +2283,9 @@ ade_status ade_istft_forward(ade_handle h, const float* d_spec, int batch, int f
 // ---- streaming entry points ---------------------------------------------------------------------------------------------
 // A stream of a sub-engine (NKF-AEC, DFSMN-AEC): the sub-engine owns the carried state and the kernels (SubEngine::stream_*), this side the handle, the staging and the rules.
 static ade_status sub_stream_create(ade_handle h, int n_streams, int frames_per_push, ade_stream_handle* out) {
-    if (h->resample || h->n_win != 1)
-        return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: " + h->meta["model_family"] + " streams take int16 PCM in and out at the model rate (16000 Hz); this handle has float audio tensors, "
-                                            "another sample rate or batch-fold");
+    if (h->resample || h->n_win != 1 || h->sub->stream_windows() != 1)
+        return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: " + h->meta["model_family"] + " streams take int16 PCM in and out at the model rate (" + std::to_string(h->sample_rate) +
+                                            " Hz); this handle has float audio tensors, another sample rate or batch-fold");
     if (n_streams < 1 || frames_per_push < 1 || frames_per_push > 4096)
         return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_create: need n_streams >= 1 and 1 <= frames_per_push <= 4096");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2292,6 +2293,7 @@ static ade_status sub_stream_create(ade_handle h, int n_streams, int frames_per_
     st->e = h; st->device = h->device; st->S = n_streams; st->N = frames_per_push;
     st->in_ch = h->sub->stream_channels();
     st->delay = h->sub->stream_delay();
+    st->hop = h->sub->stream_hop();
     h->live_streams.push_back(st);
     std::string serr;
     const int rc = h->sub->stream_create(n_streams, frames_per_push, &st->sub_state, serr);
@@ -2299,7 +2301,7 @@ static ade_status sub_stream_create(ade_handle h, int n_streams, int frames_per_
         ade_stream_destroy(st);
         return fail(h, (ade_status)rc, serr);
     }
-    const size_t S = (size_t)n_streams, P = (size_t)frames_per_push * kHop, n_in = S * st->in_ch * P, n_out = S * (P > (size_t)st->delay ? P : (size_t)st->delay);
+    const size_t S = (size_t)n_streams, P = (size_t)frames_per_push * st->hop, n_in = S * st->in_ch * P, n_out = S * (P > (size_t)st->delay ? P : (size_t)st->delay);
     if (hipMalloc((void**)&st->d_in, n_in * sizeof(int16_t)) != hipSuccess || hipMalloc((void**)&st->d_out, n_out * sizeof(int16_t)) != hipSuccess ||
         hipMalloc((void**)&st->d_f32, n_out * sizeof(float)) != hipSuccess ||
         hipHostMalloc((void**)&st->h_in, n_in * sizeof(int16_t), hipHostMallocDefault) != hipSuccess ||
@@ -2333,13 +2335,19 @@ ade_status ade_stream_delay(ade_stream_handle st, int* samples) {
     return ADE_OK;
 }
 
+ade_status ade_stream_hop(ade_stream_handle st, int* samples) {
+    if (!st || !st->e || !samples) return ADE_ERR_BAD_VALUE;
+    *samples = st->hop;
+    return ADE_OK;
+}
+
 ade_status ade_stream_create(ade_handle h, int n_streams, int frames_per_push, ade_stream_handle* out) {
     if (!out) return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_create: out is NULL");
     *out = nullptr;
     if (!h) return ADE_ERR_BAD_VALUE;
     if (h->sub && h->sub->stream_delay() > 0) return sub_stream_create(h, n_streams, frames_per_push, out);
     if (h->sub || h->n_win != 1 || h->gt_sand)
-        return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: streaming is implemented for plain GTCRN, NKF-AEC and DFSMN-AEC handles (int16 audio at the model rate)");
+        return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: streaming is implemented for plain GTCRN, NKF-AEC, DFSMN-AEC and DFSMN handles (int16 audio at the model rate)");
     if (n_streams < 1 || frames_per_push < 2 || frames_per_push > 4096)
         return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_create: need n_streams >= 1 and 2 <= frames_per_push <= 4096 (the first push reflects 257 samples)");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2476,7 +2484,7 @@ ade_status ade_stream_push(ade_stream_handle st, const int16_t* in, int16_t* out
     ade_engine* h = st->e;
     if (st->flushed) return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_push: the stream was flushed; reset it first");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = (size_t)st->S * st->N * kHop, n_in = n * st->in_ch;
+    const size_t n = (size_t)st->S * st->N * st->hop, n_in = n * st->in_ch;
     memcpy(st->h_in, in, n_in * sizeof(int16_t));
     HIP_TRY(h, hipMemcpyAsync(st->d_in, st->h_in, n_in * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
     if (st->sub_state) {

@@ -274,9 +274,11 @@ struct SubEngine {
     virtual void set_exchange_wait_ticks(int) {}
     // Stateful streaming (ade_stream_* in include/ade.h).  A sub-engine that streams owns its stream state behind an opaque pointer; the engine keeps the caller's handle,
     // the host staging and the pushed / flushed bookkeeping and forwards here.  All pointers are device memory, everything is enqueued on `s` without a synchronise.
-    // stream_channels() PCM rows of frames_per_push * 256 samples in per stream, one row out; stream_delay() = samples the output lags the input = the flush length
-    // (0: the family does not stream).
+    // stream_channels() PCM rows of frames_per_push * stream_hop() samples in per stream, one row out; stream_delay() = samples the output lags the input = the flush
+    // length (0: the family does not stream).  stream_windows() != 1: the handle folds its call into windows, which this family's stream does not compute (refused).
     virtual int stream_delay() const { return 0; }
+    virtual int stream_hop() const { return 256; }
+    virtual int stream_windows() const { return 1; }
     virtual int stream_channels() const { return channels(); }
     virtual int stream_create(int /*n_streams*/, int /*frames_per_push*/, void** /*state*/, std::string& err) {
         err = "streaming is not implemented for this model family";

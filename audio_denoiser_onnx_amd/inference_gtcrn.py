@@ -204,17 +204,18 @@ def denoise(session: InferenceSession, audio: np.ndarray, sequential: bool = Fal
 def denoise_streaming(session: InferenceSession, audio: np.ndarray, frames_per_push: int = 62) -> np.ndarray:
     """int16 mono waveform -> int16 denoised waveform of the same length through ONE stateful stream (``--stream N``): no slice edges --
     the result is what the reference's graph would give on the whole file in one call (without its whole-call DC removal), which its
-    static export cannot do for files longer than the graph input.  The file is zero-padded to whole pushes; the stream's one-hop latency
-    is removed again (pushes + flush, first hop dropped)."""
+    static export cannot do for files longer than the graph input.  The file is zero-padded to whole pushes; the stream's latency
+    (``delay``: one hop, 256 samples for GTCRN, 960 for DFSMN) is removed again (pushes + flush, the first ``delay`` samples dropped)."""
     from .session import StreamingSession
-    P = frames_per_push * 256
-    n = max(1, -(-len(audio) // P))
-    padded = np.zeros(n * P, np.int16)
-    padded[:len(audio)] = audio
     with StreamingSession(session, 1, frames_per_push) as st:
+        P = st.samples_per_push
+        n = max(1, -(-len(audio) // P))
+        padded = np.zeros(n * P, np.int16)
+        padded[:len(audio)] = audio
         parts = [st.push(padded[None, i * P:(i + 1) * P]) for i in range(n)]
         parts.append(st.flush())
-    return np.ascontiguousarray(np.concatenate(parts, axis=1)[0, 256:256 + len(audio)])
+        delay = st.delay
+    return np.ascontiguousarray(np.concatenate(parts, axis=1)[0, delay:delay + len(audio)])
 
 
 def main(argv=None) -> int:

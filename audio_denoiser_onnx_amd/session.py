@@ -365,16 +365,25 @@ class StreamingSession:
     either way) and ``delay`` is 1344 samples (84 ms): the outputs equal the reference's unfolded graph on the whole signal in one call, 1344 samples later,
     whatever the push size, bit for bit.  This family has no whole-call DC removal, so that holds for any input.  ``flush`` (1344 samples) ends the signal and
     needs a length the reference's static export accepts: the hops pushed a multiple of 5.  A stream returns audio only, also when the manifest has
-    ``output_vad_result = 1``; folded and unfolded manifests stream alike (a stream does not use the window length)."""
+    ``output_vad_result = 1``; folded and unfolded manifests stream alike (a stream does not use the window length).
+
+    On a DFSMN session (48 kHz) a hop is 960 samples (``hop``, ``ade_stream_hop``), so ``samples_per_push = frames_per_push * 960``, and ``delay`` is 960 samples
+    (20 ms).  The model is causal from end to end -- per-frame Kaldi mean, no centre padding, a memory that looks ``lorder - 1`` frames back -- so the stream carries
+    the last 960 input samples, every layer's ``lorder - 1`` frames of memory history and the second half of the last synthesised frame, and pushes plus the flush
+    equal the reference's one call on the whole signal, 960 samples later, whatever the push size, bit for bit.  ``flush`` (960 samples) needs at least two hops
+    pushed.  Only unfolded int16 handles at 48 kHz in and out stream; the bits of ``process`` on the same signal are not promised (its kernels transform frames in
+    pairs), both are within the family's gates of the oracle."""
 
     def __init__(self, session: InferenceSession, n_streams: int, frames_per_push: int):
         self._lib, self._session = session._lib, session
-        self.n_streams, self.frames_per_push, self.samples_per_push = int(n_streams), int(frames_per_push), int(frames_per_push) * 256
+        self.n_streams, self.frames_per_push = int(n_streams), int(frames_per_push)
         self._h = C.c_void_p()
         self._lib.check(self._lib.c.ade_stream_create(session._h, self.n_streams, self.frames_per_push, C.byref(self._h)), session._h)
-        delay = C.c_int(0)
+        delay, hop = C.c_int(0), C.c_int(0)
         self._lib.check(self._lib.c.ade_stream_delay(self._h, C.byref(delay)), session._h)
-        self.delay = int(delay.value)
+        self._lib.check(self._lib.c.ade_stream_hop(self._h, C.byref(hop)), session._h)
+        self.delay, self.hop = int(delay.value), int(hop.value)
+        self.samples_per_push = self.frames_per_push * self.hop
         self.in_channels = 2 if getattr(session, "_aec", False) else 1
         self._in_shape = (self.n_streams, 2, self.samples_per_push) if self.in_channels == 2 else (self.n_streams, self.samples_per_push)
         self._out_shape = (self.n_streams, self.samples_per_push)
@@ -416,7 +425,8 @@ class StreamingSession:
 
     def flush(self, want_f32: bool = False):
         """End of the signal: the last hop, int16 (n_streams, 256).  ``concatenate(pushes + [flush])[:, 256:]`` is then exactly the one-shot
-        output of the whole signal.  ``reset()`` before pushing again.  In general the flush is ``delay`` samples long (768 for NKF-AEC, 1344 for DFSMN-AEC)."""
+        output of the whole signal.  ``reset()`` before pushing again.  In general the flush is ``delay`` samples long (768 for NKF-AEC, 1344 for DFSMN-AEC,
+        960 for DFSMN)."""
         out = np.empty((self.n_streams, self.delay), np.int16)
         f32 = np.empty((self.n_streams, self.delay), np.float32) if want_f32 else None
         self._lib.check(self._lib.c.ade_stream_flush(self._h, out.ctypes.data, f32.ctypes.data if want_f32 else None), self._session._h)

@@ -177,12 +177,15 @@ ade_status ade_istft_forward(ade_handle h, const float* d_spec, int batch, int f
  * on the whole signal in one call (every op of the network is causal in time), with two stated differences: the output is one
  * hop (256 samples, 16 ms) behind the input -- a frame is complete one hop after its centre -- with the stream's first hop zero;
  * and the per-call DC removal of GTCRN_CUSTOM.forward (Export_GTCRN.py:647, a mean over the WHOLE call, not computable causally)
- * is not applied.  Plain GTCRN handles (not batch-fold; of the other model families NKF-AEC and DFSMN-AEC stream, see below).  All streams of a handle advance together.
+ * is not applied.  Plain GTCRN handles (not batch-fold; of the other model families NKF-AEC, DFSMN-AEC and DFSMN stream, see below).  All streams of a handle advance
+ * together.  A push is frames_per_push HOPS of ade_stream_hop samples: 256 at 16 kHz for GTCRN, NKF-AEC and DFSMN-AEC, 960 at 48 kHz for DFSMN.  A handle that cannot
+ * stream answers ADE_ERR_UNSUPPORTED with a message that names what its family's streams take: int16 PCM in and out at the handle's own model rate (16000 or 48000 Hz).
  * A push of up to 512 frames is ONE kernel launch (the fused chunk kernel continuing from the state its previous launch left); longer pushes, or a
  * stream created while the option "fused" is 0, take the multi-kernel sequence. */
 typedef struct ade_stream* ade_stream_handle;
 ade_status ade_stream_create(ade_handle h, int n_streams, int frames_per_push, ade_stream_handle* out);
-/* in / out: [n_streams][frames_per_push * 256] int16 (out_f32 optional float, pre-PCM-tail), caller-owned HOST buffers; synchronous. */
+/* in / out: [n_streams][frames_per_push * hop] int16 (out_f32 optional float, pre-PCM-tail), caller-owned HOST buffers; synchronous.  hop = ade_stream_hop: 256, or 960
+ * for a DFSMN stream. */
 ade_status ade_stream_push(ade_stream_handle s, const int16_t* in, int16_t* out_pcm, float* out_f32);
 /* the same on DEVICE buffers; enqueues on `hip_stream` (NULL = the engine's stream, then synchronous). */
 ade_status ade_stream_push_device(ade_stream_handle s, const int16_t* d_in, int16_t* d_out_pcm, float* d_out_f32, void* hip_stream);
@@ -192,8 +195,11 @@ ade_status ade_stream_push_device(ade_stream_handle s, const int16_t* d_in, int1
 ade_status ade_stream_flush(ade_stream_handle s, int16_t* out_pcm, float* out_f32);
 ade_status ade_stream_reset(ade_stream_handle s);      /* back to a fresh stream (zero state, next push reflects its head) */
 void ade_stream_destroy(ade_stream_handle s);           /* before ade_destroy of its engine */
-/* Samples the stream's output lags its input, which is also the flush length per stream: 256 for a GTCRN stream, 768 for an NKF-AEC stream, 1344 for a DFSMN-AEC stream. */
+/* Samples the stream's output lags its input, which is also the flush length per stream: 256 for a GTCRN stream, 768 for an NKF-AEC stream, 1344 for a DFSMN-AEC stream,
+ * 960 for a DFSMN stream. */
 ade_status ade_stream_delay(ade_stream_handle s, int* samples);
+/* Samples of one hop, the unit of frames_per_push: 256 for a GTCRN, NKF-AEC or DFSMN-AEC stream (16 kHz), 960 for a DFSMN stream (48 kHz). */
+ade_status ade_stream_hop(ade_stream_handle s, int* samples);
 
 /* ---- stateful streaming over the NKF-AEC path (model_family "nkf_aec"; the same entry points) -------------------------------
  * An echo canceller is an adaptive filter: it is useful while it keeps the echo path it has learnt.  The one-shot call, like the
@@ -254,6 +260,34 @@ ade_status ade_stream_delay(ade_stream_handle s, int* samples);
  * one frame per FFT; the one-shot kernel's pairs would make a frame's rounding depend on where the push ends), the memory sums its
  * taps in the one-shot order from a per-layer history of dilation * (lorder - 1) frames, and the overlap-add adds at most two frames
  * in ascending order and reads the one-shot's 1 / window-square table. */
+
+/* ---- stateful streaming over the DFSMN path (model_family "dfsmn", 48 kHz; the same entry points) ------------------------------
+ * DFSMN.forward (Export_DFSMN.py:176-246) is causal from end to end: the Kaldi mean is taken per frame (no whole-call DC removal),
+ * there is no centre padding (frame t covers the samples [960 t, 960 t + 1920)), every layer of the mask network is frame-local
+ * except the depthwise memory, which looks lorder - 1 frames back over a zero pad, and the synthesis is a two-frame overlap-add.  So
+ * pushes plus the flush equal the reference's ONE call on the whole signal, one hop (960 samples, 20 ms) later, within the family's
+ * gates (waveform 2e-5, PCM 1 LSB from the exact-table oracle), where the per-slice driver restarts the nine memories and divides
+ * its one-frame edges by w^2 ~ 0.0064.  A stream carries, per independent stream: the last 960 input samples, per layer the last
+ * lorder - 1 frames of the projection output, and the second half of the last synthesised frame.
+ * Eligible handles: int16 audio at 48 kHz on both sides, not folded (F32 / F16 audio tensors, another input or output rate, or
+ * use_batch_fold = 1 -- a folded call treats its windows as independent clips, which is not what a stream computes --:
+ * ADE_ERR_UNSUPPORTED, the message names int16 / 48000).  Static and dynamic_axes manifests both stream; a stream does not use the
+ * window length.
+ * Buffers: in [n_streams][960 F] int16, F = frames_per_push hops (ade_stream_hop = 960); out the same shape; out_f32 optional float
+ * of the same shape (the waveform before the PCM tail).  1 <= F <= 4096.  All streams of a handle advance together.
+ * ade_stream_push_device enqueues on the caller's stream and does not synchronise.
+ * Output timing: the stream's first 960 output samples are zero; output sample j of the stream is sample j - 960 of the one-call
+ * result.  A fresh stream's first push completes F - 1 frames, every later push F.  With F = 1 the first push completes none: it
+ * returns 960 zeros and runs no network kernel (it only stores the carried samples).
+ * ade_stream_flush returns the last 960 samples per stream (out [n_streams][960]): the second half of the last frame over
+ * w^2[960 + n].  It ends a signal of 960 K samples after K hops, equal to the static export with input_audio_length = 960 K.  It
+ * needs K >= 2, one whole frame; otherwise ADE_ERR_BAD_VALUE with a message that says so (the stream stays usable).  After a flush
+ * the stream must be reset before it is pushed again.
+ * The push size does not change a bit of the output, PCM and f32, and a stream's bits do not depend on how many other streams share
+ * the handle: every transform holds ONE frame (each real transform is a half-length complex FFT plus a split pass), the memory sums
+ * its taps in one order from history or push alike, the overlap-add adds at most two frames in ascending order.
+ * NOT promised: the bits of ade_process on the same signal.  The one-shot kernels transform frames in pairs, which a stream must not
+ * (a frame's rounding would depend on where a push ends); both are held to the same gates against the oracle. */
 
 /* ---- generic STFT_Process operator: any n_fft / win_length / hop / window, for the other model families -------
  * Replaces the reference's STFT_Process module in its 'stft_B' (packed) and 'istft_B' (packed, static_norm=True) forms

@@ -12,6 +12,7 @@ Everything else -- the fused fbank|STFT analysis kernel, log-mel, the inlined ma
 tail -- is the reference's own code path.
 
     python tools/make_golden_dfsmn.py      # writes tests/golden/dfsmn_seed0.adew + dfsmn_seed0_io.npz
+    python tools/make_golden_dfsmn.py --stream      # writes tests/golden/dfsmn_seed0_stream.npz (one call on 48 000 samples, for the streaming tests)
 """
 import ast
 import os
@@ -203,6 +204,29 @@ def float_io_fixture():
         print(tag, y.shape, y.dtype, float(np.abs(y).max()))
     np.savez_compressed(os.path.join(mg.GOLD, "dfsmn_float_io_seed0.npz"), **out)
 
+
+def stream_fixture():
+    """The streaming tests' longer reference run (tests/golden/dfsmn_seed0_stream.npz): the reference's own forward at INPUT_AUDIO_LENGTH = 48000 -- 50 hops, 49 frames,
+    2.5 x the reach of the memory -- in ONE call on one speech clip: ``pcm_in``, ``pcm_out`` and ``wave``, the float waveform before the PCM tail (the same graph
+    with OUT_AUDIO_DTYPE = F32, which leaves out the * 32768 and the clamp, :241-247).  Data only; the network is dfsmn_seed0.adew's."""
+    L = 48000
+    wav = mg.load_wav_i16(os.path.join(REF_ROOT, "Test_Examples", "denoise", "speech_with_noise_48k.wav"))
+    pcm = wav[72000:72000 + L].copy()
+    assert pcm.shape == (L,)
+    out = {"pcm_in": pcm}
+    for key, dout in (("pcm_out", "INT16"), ("wave", "F32")):
+        ns, model = build(0, L, {"OUT_AUDIO_DTYPE": dout})
+        assert ns["STFT_SIGNAL_LENGTH"] == 49
+        with torch.inference_mode():
+            out[key] = model(torch.from_numpy(pcm.reshape(1, 1, -1).copy())).numpy().reshape(-1)
+    assert out["pcm_out"].dtype == np.int16 and out["wave"].dtype == np.float32 and out["pcm_out"].shape == out["wave"].shape == (L,)
+    np.savez_compressed(os.path.join(mg.GOLD, "dfsmn_seed0_stream.npz"), **out)
+    print("stream:", out["pcm_in"].shape, "->", out["pcm_out"].shape, int(np.abs(out["pcm_out"]).max()))
+
+
+if __name__ == "__main__" and "--stream" in sys.argv:
+    stream_fixture()
+    sys.exit(0)
 
 if __name__ == "__main__" and "--dynamic" in sys.argv:
     dynamic_fixture()
