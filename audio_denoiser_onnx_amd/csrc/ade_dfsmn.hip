@@ -191,13 +191,7 @@ __global__ __launch_bounds__(256) void k_dfsmn_ola_pcm(const float* __restrict__
 // ---- streams ----------------------------------------------------------------------------------------------------------------------------------------------------
 constexpr int kHalfK = kKaldiNfft / 2, kHalfS = kNfftD / 2;      // 1024, 960: the complex lengths of the two real transforms
 
-// A real transform of n = 2 h samples from the h-point complex FFT Z of z[m] = x[2 m] + i x[2 m + 1]:  X[f] = E[f] + w_n^f O[f],  f <= h, with
-// E[f] = (Z[f] + conj Z[h - f]) / 2 (the even samples' transform) and O[f] = (Z[f] - conj Z[h - f]) / (2 i) (the odd samples'); Z[h] = Z[0].
-__device__ __forceinline__ float2 split_bin(const float2* __restrict__ r, int f, int h, const float2* __restrict__ tw) {
-    const float2 z = r[f == h ? 0 : f], zc = r[f == 0 ? 0 : h - f];
-    const float2 e = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y)), o = make_float2(0.5f * (z.y + zc.y), 0.5f * (zc.x - z.x));
-    return fft::cadd(e, fft::cmul(tw[f], o));
-}
+using fft::split_bin;      // a real transform as a half-length complex one plus a split pass (ade_fft.h)
 
 // One workgroup per frame the push completes, plus one per stream that renews the carried input.  A stream's row is [960 carried samples | the push's 960 F samples];
 // completed frame i of stream s (column s * Mp + i) covers row samples [off + 960 i, off + 960 i + 1920): off = 0, or 960 on a fresh stream, whose carried samples are

@@ -2281,7 +2281,7 @@ ade_status ade_istft_forward(ade_handle h, const float* d_spec, int batch, int f
 
 
 // ---- streaming entry points ---------------------------------------------------------------------------------------------
-// A stream of a sub-engine (NKF-AEC, DFSMN-AEC): the sub-engine owns the carried state and the kernels (SubEngine::stream_*), this side the handle, the staging and the rules.
+// A stream of a sub-engine (NKF-AEC, DFSMN-AEC, DFSMN, UL-UNAS): the sub-engine owns the carried state and the kernels (SubEngine::stream_*), this side the handle, the staging and the rules.
 static ade_status sub_stream_create(ade_handle h, int n_streams, int frames_per_push, ade_stream_handle* out) {
     if (h->resample || h->n_win != 1 || h->sub->stream_windows() != 1)
         return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: " + h->meta["model_family"] + " streams take int16 PCM in and out at the model rate (" + std::to_string(h->sample_rate) +
@@ -2347,7 +2347,7 @@ ade_status ade_stream_create(ade_handle h, int n_streams, int frames_per_push, a
     if (!h) return ADE_ERR_BAD_VALUE;
     if (h->sub && h->sub->stream_delay() > 0) return sub_stream_create(h, n_streams, frames_per_push, out);
     if (h->sub || h->n_win != 1 || h->gt_sand)
-        return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: streaming is implemented for plain GTCRN, NKF-AEC, DFSMN-AEC and DFSMN handles (int16 audio at the model rate)");
+        return fail(h, ADE_ERR_UNSUPPORTED, "ade_stream_create: streaming is implemented for plain GTCRN, NKF-AEC, DFSMN-AEC, DFSMN and UL-UNAS handles (int16 audio at the model rate)");
     if (n_streams < 1 || frames_per_push < 2 || frames_per_push > 4096)
         return fail(h, ADE_ERR_BAD_VALUE, "ade_stream_create: need n_streams >= 1 and 2 <= frames_per_push <= 4096 (the first push reflects 257 samples)");
     HIP_TRY(h, hipSetDevice(h->device));

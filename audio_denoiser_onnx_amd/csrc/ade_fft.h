@@ -110,6 +110,22 @@ __device__ __forceinline__ float2* forward(float2* a, float2* b, const Plan& p, 
     return in;
 }
 
+// A real transform of n = 2 h samples from the h-point complex FFT Z of z[m] = x[2 m] + i x[2 m + 1]:  X[f] = E[f] + w_n^f O[f],  f <= h, with
+// E[f] = (Z[f] + conj Z[h - f]) / 2 (the even samples' transform) and O[f] = (Z[f] - conj Z[h - f]) / (2 i) (the odd samples'); Z[h] = Z[0].
+// r: the h-point result of forward(); tw: the n-point table.  One frame per transform: what the streams use, whose frames must not share a transform with a neighbour.
+__device__ __forceinline__ float2 split_bin(const float2* __restrict__ r, int f, int h, const float2* __restrict__ tw) {
+    const float2 z = r[f == h ? 0 : f], zc = r[f == 0 ? 0 : h - f];
+    const float2 e = make_float2(0.5f * (z.x + zc.x), 0.5f * (z.y - zc.y)), o = make_float2(0.5f * (z.y + zc.y), 0.5f * (zc.x - z.x));
+    return cadd(e, cmul(tw[f], o));
+}
+// The way back: bin f < h of the h-point complex spectrum whose INVERSE transform is x[2 m] + i x[2 m + 1], from the half spectrum X of a real frame of n = 2 h samples (a = X[f],
+// b = X[h - f], t = tw_n[f]), already conjugated for conj(DFT_h(conj W)):  W[f] = (X[f] + conj X[h - f]) + i (X[f] - conj X[h - f]) e^{+2 pi i f / n}.
+__device__ __forceinline__ float2 merge_bin_conj(float2 a, float2 b, float2 t) {
+    const float2 sm = make_float2(a.x + b.x, a.y - b.y), d = make_float2(a.x - b.x, a.y + b.y);
+    const float2 dt = make_float2(d.x * t.x + d.y * t.y, d.y * t.x - d.x * t.y);
+    return make_float2(sm.x - dt.y, -(sm.y + dt.x));
+}
+
 // ---- the same passes with the transform size and its radices known at compile time (the starred models' sizes, and two small ones the host-simulator tests use): trip counts,
 // `j % ns` and the twiddle strides fold into constants, the pass loop unrolls.  The factorisation is make_plan's (4s, then 2s, 3s, 5s), so a size's results are bit-identical
 // to the run-time plan's.

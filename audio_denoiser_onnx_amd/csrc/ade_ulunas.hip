@@ -13,12 +13,14 @@
 // The DPGRNN blocks ARE GTCRN's (same widths: 33 bins x 16 channels) and reuse its multi-kernel path (ade_kernels.hip); the STFT
 // pair is the generic operator of ade_stft.hip (dense windowed DFT on the matrix cores, exact-angle tables).
 #include "ade_device.h"
+#include "ade_fft.h"
 #include "ade_internal.h"
 #include "../../include/ade.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <type_traits>
 
 namespace ade {
@@ -183,23 +185,53 @@ __device__ __forceinline__ void frame_stats(const float* __restrict__ orow, floa
     }
 }
 
+// Where k_ulu_conv takes its input frames from.  stage(): tap frame tt of row b into dst (tt < 0: before the row's first frame); keep(): called with the staged
+// frame t itself, already summed with the second input.
+struct ClipFrames {            // a whole clip per row: nothing precedes frame 0
+    const float *x, *x2;
+    __device__ __forceinline__ void stage(float* __restrict__ dst, long long b, int tt, int T, int row) const {
+        const size_t at = ((size_t)b * T + (tt < 0 ? 0 : tt)) * row;
+        for (int i = threadIdx.x; i < row; i += 256) dst[i] = tt < 0 ? 0.0f : (x2 ? x[at + i] + x2[at + i] : x[at + i]);
+    }
+    __device__ __forceinline__ void keep(const float*, long long, int, int, int) const {}
+};
+// A push of T frames per stream (row b = stream): the Hk = kt - 1 frames before it come from the stream's history hist_in [stream][Hk][row], oldest first -- zeros on a
+// fresh stream, the reset's memset -- and the push's last Hk staged frames become hist_out (the OTHER buffer of a ping-pong pair: workgroups of this launch still read
+// hist_in).  T >= Hk, so the next history is always whole frames of this push; hist_out null: the flush, after which the stream is reset.
+struct PushFrames {
+    const float *x, *x2, *hist_in;
+    float* hist_out;
+    int Hk;
+    __device__ __forceinline__ void stage(float* __restrict__ dst, long long b, int tt, int T, int row) const {
+        if (tt < 0) {
+            const float* h = hist_in + ((size_t)b * Hk + (Hk + tt)) * row;
+            for (int i = threadIdx.x; i < row; i += 256) dst[i] = h[i];
+            return;
+        }
+        const size_t at = ((size_t)b * T + tt) * row;
+        for (int i = threadIdx.x; i < row; i += 256) dst[i] = x2 ? x[at + i] + x2[at + i] : x[at + i];
+    }
+    __device__ __forceinline__ void keep(const float* __restrict__ cur, long long b, int t, int T, int row) const {
+        const int q = t - (T - Hk);
+        if (!hist_out || q < 0) return;
+        float* h = hist_out + ((size_t)b * Hk + q) * row;
+        for (int i = threadIdx.x; i < row; i += 256) h[i] = cur[i];       // (elements this thread staged itself: no barrier needed)
+    }
+};
+
 // out[b][t][fo][co] = act(bias + sum over taps / group channels), causal in t (:222-238, :264-267); optional second input added first (:648).
 // One workgroup per frame: the kt input frames it needs (already summed with the skip tensor) and the whole weight tensor are staged in LDS
 // once, so HBM / L2 sees every input element kt times instead of once per tap, channel and output.
-template <int KT, int KF, int STRIDE, bool DECONV>
-__global__ __launch_bounds__(256) void k_ulu_conv(const float* __restrict__ x, const float* __restrict__ x2, ConvDesc d, float* __restrict__ out, int T, int wsize,
-                                                  float* __restrict__ zt, float* __restrict__ pfreq) {
+template <int KT, int KF, int STRIDE, bool DECONV, class Src>
+__global__ __launch_bounds__(256) void k_ulu_conv(Src src, ConvDesc d, float* __restrict__ out, int T, int wsize, float* __restrict__ zt, float* __restrict__ pfreq) {
     HIP_DYNAMIC_SHARED(float, lds)
     const long long frame = blockIdx.x;
     const long long b = frame / T;
     const int t = (int)(frame - b * T), row = d.Fi * d.Cin;
     float* xin = lds;                      // [kt][Fi * Cin]
     float* wl = lds + KT * row;          // the weights in their torch layout
-    for (int a = 0; a < KT; ++a) {
-        const int tt = DECONV ? t - a : t - (KT - 1) + a;
-        const size_t at = ((size_t)b * T + (tt < 0 ? 0 : tt)) * row;
-        for (int i = threadIdx.x; i < row; i += 256) xin[a * row + i] = tt < 0 ? 0.0f : (x2 ? x[at + i] + x2[at + i] : x[at + i]);
-    }
+    for (int a = 0; a < KT; ++a) src.stage(xin + a * row, b, DECONV ? t - a : t - (KT - 1) + a, T, row);
+    if constexpr (KT > 1) src.keep(xin + (DECONV ? 0 : KT - 1) * row, b, t, T, row);
     for (int i = threadIdx.x; i < wsize; i += 256) wl[i] = d.w[i];
     __syncthreads();
     float* orow = out + (size_t)frame * d.Fo * d.Cout;
@@ -217,7 +249,7 @@ __global__ __launch_bounds__(256) void k_ulu_conv(const float* __restrict__ x, c
 template <int C>               // compile-time channel count: the k loops unroll and their LDS reads pipeline
 __global__ __launch_bounds__(256) void k_ulu_ta(const float* __restrict__ zt, const float* __restrict__ wih_t, const float* __restrict__ whh_t,
                                                 const float* __restrict__ bih, const float* __restrict__ bhh, const float* __restrict__ fc_t,
-                                                const float* __restrict__ fc_b, float* __restrict__ at, int T) {
+                                                const float* __restrict__ fc_b, float* __restrict__ at, int T, float* __restrict__ state) {
     HIP_DYNAMIC_SHARED(float, lds)
     __shared__ float hs[64];
     __shared__ float part[4][6][64];
@@ -235,8 +267,8 @@ __global__ __launch_bounds__(256) void k_ulu_ta(const float* __restrict__ zt, co
     if (unit && p == 0)
         for (int g = 0; g < 3; ++g) { bi[g] = bih[g * H + j]; bh[g] = bhh[g * H + j]; }
     const float fb = (p == 0 && j < C) ? fc_b[j] : 0.0f;
-    float h = 0.0f;
-    if (tid < 64) hs[tid] = 0.0f;
+    float h = (state && unit && p == 0) ? state[(size_t)b * H + j] : 0.0f;       // streams: the hidden state the previous push left ([clip][2C]; null: a whole clip)
+    if (tid < 64) hs[tid] = (state && tid < H) ? state[(size_t)b * H + tid] : 0.0f;
     __syncthreads();
     for (int t = 0; t < T; ++t) {
         if ((t & 63) == 0) {
@@ -289,6 +321,7 @@ __global__ __launch_bounds__(256) void k_ulu_ta(const float* __restrict__ zt, co
             at[((size_t)b * T + t) * C + j] = usig(a);
         }
     }
+    if (state && p == 0 && unit) state[(size_t)b * H + j] = h;
 }
 
 // The same time attention with the recurrence on ONE wavefront and nothing but the recurrence inside it (round 5).  k_ulu_ta spreads every step's contraction over four
@@ -301,7 +334,7 @@ __global__ __launch_bounds__(256) void k_ulu_ta(const float* __restrict__ zt, co
 template <int C>
 __global__ __launch_bounds__(256) void k_ulu_ta2(const float* __restrict__ zt, const float* __restrict__ wih_t, const float* __restrict__ whh_t,
                                                  const float* __restrict__ bih, const float* __restrict__ bhh, const float* __restrict__ fc_t,
-                                                 const float* __restrict__ fc_b, float* __restrict__ at, int T) {
+                                                 const float* __restrict__ fc_b, float* __restrict__ at, int T, float* __restrict__ state) {
     HIP_DYNAMIC_SHARED(float, lds)
     constexpr int H = 2 * C, G = 3 * H;
     const int b = blockIdx.x, tid = threadIdx.x, j = tid & 63;
@@ -326,7 +359,9 @@ __global__ __launch_bounds__(256) void k_ulu_ta2(const float* __restrict__ zt, c
 #pragma unroll
         for (int k = 0; k < H; ++k) { wrz[k] = mk2(0.0f, 0.0f); if (!kNLds) wn[k] = 0.0f; }
     }
-    float h = 0.0f;
+    // streams: h continues from the state the previous push left ([clip][2C]; null: a whole clip).  The chunks below only decide WHEN a frame's projections are formed, every
+    // frame's sums are its own and the recurrence is one chain: where a push ends relative to a chunk changes no bit.
+    float h = (state && tid < 64) ? state[(size_t)b * H + u] : 0.0f;
     for (int t0 = 0; t0 < T; t0 += 64) {
         const int nt = min(64, T - t0);
         __syncthreads();                      // (the previous chunk's phase 3 is done with s_h; first pass: the weights are staged)
@@ -368,6 +403,7 @@ __global__ __launch_bounds__(256) void k_ulu_ta2(const float* __restrict__ zt, c
             at[((size_t)b * T + t0) * C + o] = usig(a);
         }
     }
+    if (state && tid < H) state[(size_t)b * H + tid] = h;       // (H <= 64: wavefront 0, lane = unit)
 }
 
 // frequency attention GRUs (:151-153): per frame, the zero-padded bin powers in groups of 4 are a sequence of H steps through a
@@ -488,6 +524,135 @@ __global__ __launch_bounds__(256) void k_ulu_f2pcm(const float* __restrict__ y, 
     if (pcm) pcm[i] = (int16_t)(int)fminf(fmaxf(v * 32767.0f, -32768.0f), 32767.0f);
 }
 
+// ---- streams (ade_stream_* on a ul_unas handle, include/ade.h) ---------------------------------------------------------------------------------
+// The model is causal from end to end, so a push of F hops continues the signal one hop behind the input: frame g is centred on sample 256 g and complete when
+// 256 (g + 1) samples have arrived.  A push completes F frames (a fresh stream's first push: frames 0 .. F - 1, the head reflected), the flush frame K of a signal of
+// 256 K samples (the tail reflected).  Per push, all on the caller's ONE stream:
+//   k_ulu_stream_analysis   [257 carried | 256 F new] -> spectrum in the (stream, 2 x 257, F) layout k_ulu_feat / k_ulu_mask read; renews the carried samples
+//   the network             run_net() with T = F: k_ulu_conv<.., PushFrames> for the kt > 1 convolutions, the time attention from its state, k_ulu_stream_inter_gru
+//   k_ulu_stream_synthesis  the Hermitian inverse of ONE frame as a 256-point complex transform, windowed
+//   k_ulu_stream_out        overlap-add with the carried half frame / the steady window-square sum, the PCM tail of k_ulu_f2pcm, the next carried half
+// ONE frame per transform (a 512-point real transform = a 256-point complex one plus a split pass, ade_fft.h): the one-shot path's generic STFT rides two frames on one
+// complex transform, paired by the frame's parity inside the call, so its bits would move with the push size.
+constexpr int kUHalf = kUNfft / 2, kUCarry = kUHop + 1;      // 256 complex points; 257 carried samples: the tail reflection of the flush reaches sample L - 257
+
+// mode 0: a push that continues a signal; 1: a fresh stream's first push (the head reflection instead of the carried samples); 2: the flush (F = 1, the carried samples
+// and their reflection, `in` unused).  Workgroups from N on (modes 0, 1) copy the push's last 257 samples into carry_out (the other buffer of the ping-pong pair).
+__global__ __launch_bounds__(256) void k_ulu_stream_analysis(const int16_t* __restrict__ in, const int16_t* __restrict__ carry_in, int16_t* __restrict__ carry_out, int P, int F, int N,
+                                                             int mode, fft::Plan p256, const float2* __restrict__ tw256, const float2* __restrict__ tw512,
+                                                             const float* __restrict__ win, float* __restrict__ spec) {
+    __shared__ float2 A[kUHalf];
+    __shared__ float2 B[kUHalf];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= N) {
+        const int s = (int)blockIdx.x - N;
+        for (int n = tid; n < kUCarry; n += 256) carry_out[(size_t)s * kUCarry + n] = in[(size_t)s * P + (P - kUCarry) + n];
+        return;
+    }
+    const int fr = (int)blockIdx.x, s = fr / F, i = fr - s * F;
+    const int16_t *old = carry_in + (size_t)s * kUCarry, *row = in + (size_t)s * P;
+    // sample n of the frame, signal position p0 + 256 i - 256 + n with p0 the push's first sample: the carried samples are positions p0 - 257 .. p0 - 1
+    auto sample = [&](int n) {
+        int16_t v;
+        if (mode == 2) v = old[n < kUHop ? n + 1 : 2 * kUHop - 1 - n];           // second half: position L + q reflects to L - 2 - q = carried sample 255 - q
+        else if (mode == 1) { const int idx = kUHop * i - kUHop + n; v = row[idx < 0 ? -idx : idx]; }
+        else { const int r = kUHop * i + 1 + n; v = r < kUCarry ? old[r] : row[r - kUCarry]; }
+        return ((float)v * (1.0f / 32768.0f)) * win[n];
+    };
+    A[tid] = make_float2(sample(2 * tid), sample(2 * tid + 1));
+    const float2* r = fft::forward(A, B, p256, tw256, tid, 256);
+    float* sp = spec + (size_t)s * 2 * kUBins * F + i;
+    for (int f = tid; f < kUBins; f += 256) {
+        const float2 x = fft::split_bin(r, f, kUHalf, tw512);
+        sp[(size_t)f * F] = x.x;
+        sp[(size_t)(kUBins + f) * F] = x.y;
+    }
+}
+
+// The inter-frame GRU of a push: k_inter_gru's recurrence (ade_kernels.hip: per (stream, bin) column two groups of GRU(8 -> 8) along the frames, 16 lanes per column, lane =
+// group * 8 + unit, `gru` in its lane format [3 x 8 ih | 3 x 8 hh | 3 b_ih | 3 b_hh]) from the stream's state [stream][33][16], which it updates in place.  Not
+// k_inter_gru itself: that kernel walks four frames per trip and the compiler contracts h' = (1 - z) n + z h into one fused multiply-add in the first of the four and into
+// two products and a sum in the other three (gfx950 code of the build at hand), so a frame's last bit there depends on its index inside the launch modulo 4 -- nothing a
+// whole clip notices, but a stream's frames change that index with the push size.  Here: one frame per trip, and every rounding of a step spelled out.
+__global__ __launch_bounds__(256) void k_ulu_stream_inter_gru(const float* __restrict__ x, const float* __restrict__ gru, float* __restrict__ rnn, int B, int T,
+                                                              float* __restrict__ state) {
+    const int site = blockIdx.x * 16 + (threadIdx.x >> 4), q = threadIdx.x & 15, grp = q >> 3;
+    const bool live = site < B * kFw;
+    const int sc = live ? site : B * kFw - 1;            // (lanes past the last column repeat it and store nothing)
+    const int b = sc / kFw, f = sc - b * kFw;
+    const float* pk = gru + q * 54;
+    float wi[3][8], wh[3][8], bi[3], bh[3];
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { wi[g][k] = pk[g * 8 + k]; wh[g][k] = pk[24 + g * 8 + k]; }
+        bi[g] = pk[48 + g];
+        bh[g] = pk[51 + g];
+    }
+    float h = state[(size_t)sc * kCh + q];
+    const float* xb = x + ((size_t)b * T * kFw + f) * kCh + grp * 8;      // frame t at xb + t * kFw * kCh
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+        const float4 x0 = *reinterpret_cast<const float4*>(xb + (size_t)t * kFw * kCh), x1 = *reinterpret_cast<const float4*>(xb + (size_t)t * kFw * kCh + 4);
+        const float xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+        float gi[3] = {bi[0], bi[1], bi[2]}, gh[3] = {bh[0], bh[1], bh[2]};
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int g = 0; g < 3; ++g) gi[g] = fmaf(wi[g][k], xv[k], gi[g]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float hk = __shfl(h, k, 8);
+#pragma unroll
+            for (int g = 0; g < 3; ++g) gh[g] = fmaf(wh[g][k], hk, gh[g]);
+        }
+        const float r = usig(__fadd_rn(gi[0], gh[0])), z = usig(__fadd_rn(gi[1], gh[1])), n = ade::dev::tanh_f(fmaf(r, gh[2], gi[2]));
+        h = fmaf(z, h, __fmul_rn(1.0f - z, n));
+        if (live) rnn[(((size_t)b * T + t) * kFw + f) * kCh + q] = h;
+    }
+    if (live) state[(size_t)sc * kCh + q] = h;
+}
+
+// One workgroup per frame: the masked half spectrum (imaginary parts of the DC and Nyquist bins dropped, as the generic synthesis does) -> 512 windowed samples.
+__global__ __launch_bounds__(256) void k_ulu_stream_synthesis(const float* __restrict__ spec, int F, fft::Plan p256, const float2* __restrict__ tw256,
+                                                              const float2* __restrict__ tw512, const float* __restrict__ win, float* __restrict__ frames) {
+    __shared__ float2 A[kUHalf];
+    __shared__ float2 B[kUHalf];
+    const int tid = threadIdx.x, fr = (int)blockIdx.x, s = fr / F, i = fr - s * F;
+    const float* sp = spec + (size_t)s * 2 * kUBins * F + i;
+    auto bin = [&](int f) { return make_float2(sp[(size_t)f * F], f == 0 || f == kUHalf ? 0.0f : sp[(size_t)(kUBins + f) * F]); };
+    A[tid] = fft::merge_bin_conj(bin(tid), bin(kUHalf - tid), tw512[tid]);
+    const float2* r = fft::forward(A, B, p256, tw256, tid, 256);
+    float2* out = reinterpret_cast<float2*>(frames + (size_t)fr * kUNfft);
+    constexpr float inv = 1.0f / (float)kUNfft;
+    out[tid] = make_float2(__fmul_rn(r[tid].x * inv, win[2 * tid]), __fmul_rn(-r[tid].y * inv, win[2 * tid + 1]));
+}
+
+// Output hop i of a push = the second half of the frame before local frame i (the carried half for i = 0) + the first half of frame i, in that order, over den[256] =
+// the two window squares summed in the same order; a fresh stream's hop 0 is the delay: zero.  Then the PCM tail of k_ulu_f2pcm.  The threads from `total` on copy the
+// second half of the push's last frame into half_out (null: the flush).
+__global__ __launch_bounds__(256) void k_ulu_stream_out(const float* __restrict__ frames, const float* __restrict__ half_in, float* __restrict__ half_out,
+                                                        const float* __restrict__ den, int F, int fresh, int16_t* __restrict__ pcm, float* __restrict__ f32, long long total,
+                                                        long long total_all) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= total_all) return;
+    if (g >= total) {
+        const long long e = g - total;
+        const long long st = e / kUHop;
+        half_out[e] = frames[((size_t)st * F + (F - 1)) * kUNfft + kUHop + (int)(e - st * kUHop)];
+        return;
+    }
+    const long long fr = g / kUHop;                 // = stream * F + i: the output row of a stream is its F hops
+    const int n = (int)(g - fr * kUHop), i = (int)(fr % F);
+    float y = 0.0f;
+    if (!(fresh && i == 0)) {
+        const float prev = i > 0 ? frames[(size_t)(fr - 1) * kUNfft + kUHop + n] : half_in[(size_t)(fr / F) * kUHop + n];
+        y = (prev + frames[(size_t)fr * kUNfft + n]) / den[n];
+    }
+    if (f32) f32[g] = y;
+    if (pcm) pcm[g] = (int16_t)(int)fminf(fmaxf(y * 32767.0f, -32768.0f), 32767.0f);
+}
+
 int ufail(std::string& err, int st, const std::string& msg) { err = msg; return st; }
 #define UL_HIP(expr)                                                                                  \
     do {                                                                                              \
@@ -514,8 +679,16 @@ void pack_gru_lane(float* dst, const float* wih, const float* whh, const float* 
 
 }  // namespace
 
-struct UlunasEngine : SubEngine {
-    int device = 0, L = 0 /* one window */, n_win = 1, T = 0, out_len_ = 0;
+// The buffers of one pass through the network and its frame count per row: the engine's own (one call, reserve()) or, for the length of a push, a stream's.
+struct UlunasWork {
+    int T = 0;
+    float *xf = nullptr, *spec = nullptr, *yf = nullptr, *bufA = nullptr, *bufB = nullptr, *bufC = nullptr, *bufD = nullptr, *dpa = nullptr, *dpb = nullptr, *skip[5] = {}, *zt = nullptr, *pfreq = nullptr, *at = nullptr,
+          *fah = nullptr, *rnn = nullptr, *dpm = nullptr, *mask_tap = nullptr;
+};
+struct UlunasStream;
+
+struct UlunasEngine : SubEngine, UlunasWork {
+    int device = 0, L = 0 /* one window */, n_win = 1, out_len_ = 0;
     int syn_len = 0;                   // samples per row the ISTFT writes: out_len_ for a static export, 256 T (the kept tail) for a dynamic one
     bool ta2 = !(getenv("ADE_ULU_TA2") && atoi(getenv("ADE_ULU_TA2")) == 0);     // the single-wavefront time-attention kernel (k_ulu_ta2; ADE_ULU_TA2=0: the four-wavefront form)
     ade_stft_handle plan = nullptr;
@@ -526,8 +699,11 @@ struct UlunasEngine : SubEngine {
     DpPacked dp[2];
     int capacity = 0;
     float* ws = nullptr;
-    float *xf = nullptr, *spec = nullptr, *yf = nullptr, *bufA = nullptr, *bufB = nullptr, *bufC = nullptr, *bufD = nullptr, *dpa = nullptr, *dpb = nullptr, *skip[5] = {}, *zt = nullptr, *pfreq = nullptr, *at = nullptr,
-          *fah = nullptr, *rnn = nullptr, *dpm = nullptr, *mask_tap = nullptr;
+    // streams: the one-frame transforms' tables (the window make_window() gives the generic operator; den[256] = its squares summed over the two frames of a sample) and,
+    // while a push is being enqueued, the stream whose state the network continues (null: a whole clip per row)
+    const float *swin = nullptr, *sden = nullptr, *stw512 = nullptr, *stw256 = nullptr;
+    fft::Plan p256;
+    const UlunasStream* live = nullptr;
 
     // Row groups on side streams (round 5): the network between the two STFTs runs per group of rows, group k > 0 on its own stream between a fork and a join event, so that
     // one group's latency-bound launches (the time-attention recurrences: one workgroup per clip, 63 dependent steps, 20 % of the call with the chip nearly idle) run under
@@ -558,6 +734,35 @@ struct UlunasEngine : SubEngine {
     int tap(hipStream_t s, const char* name, int batch, float* out, size_t count, size_t* written, std::string& err) override;
     void ctfa(hipStream_t s, const Block& bk, const float* x, const float* res, float* out, int B, int shuffle);
     float* run_block(hipStream_t s, const Block& bk, const float* x, const float* x2, float* t0, float* t1, float* dst, int B);
+    // streams (ade_stream_*): state per stream object, see UlunasStream below
+    int stream_delay() const override { return kUHop; }
+    int stream_hop() const override { return kUHop; }
+    int stream_windows() const override { return n_win; }
+    int stream_channels() const override { return 1; }
+    int stream_create(int n_streams, int frames_per_push, void** state, std::string& err) override;
+    int stream_reset(void* state, hipStream_t s, std::string& err) override;
+    int stream_push(void* state, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) override;
+    int stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) override;
+    void stream_destroy(void* state) override;
+    int stream_step(UlunasStream* st, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err);
+};
+
+// What a stream carries between pushes, for S streams that advance together: one allocation, its leading part cleared by a reset.
+struct UlunasStream {
+    int S = 0, F = 0;                           // streams, hops per push
+    long long hops = 0;                         // hops pushed since the last reset
+    int cur = 0;                                // which buffer of every ping-pong pair holds the state
+    bool flushing = false;
+    int16_t* carry[2] = {};                     // [S][257] the last 257 input samples
+    float* hist[2] = {};                        // per convolution with kt > 1, at hist_off[block]: [S][kt - 1][Fi * Cin] its last input frames (x + skip already summed)
+    float* half[2] = {};                        // [S][256] the second half of the last synthesised frame
+    float* ta = nullptr;                        // per block, at ta_off[block]: [S][2 C] the time-attention GRU's hidden state (updated in place: one workgroup per stream)
+    float* inter[2] = {};                       // [S][33][16] the two inter-frame GRU states (in place)
+    size_t hist_off[10] = {}, ta_off[10] = {};
+    UlunasWork work;                            // one push's workspace, S * F frames
+    float* frames = nullptr;                    // [S * F][512] windowed synthesis frames
+    void* block = nullptr;
+    size_t reset_bytes = 0;
 };
 
 int ulunas_create(const std::map<std::string, Tensor>& tensors, int in_len, int n_win, int dynamic_keep, int device, SubEngine** out, std::string& err) {
@@ -668,6 +873,19 @@ int ulunas_create(const std::map<std::string, Tensor>& tensors, int in_len, int 
         if (e->blocks[i].type == 2 && e->blocks[i].cin == e->blocks[i].cout && e->blocks[i].stride == 1) ok = false;   // residual on a skip-summed input: not in this architecture
     make_block(e->blocks[9], "decoder.de_convs.4.", types[0], cin, 1, kUErb, kts[0], kfs[0], strides[0], groups[0], 1, 1);
     want(&e->erb, "erb_filters", {kUBands, kUHigh});
+    {   // streams: window, window-square sum and twiddles of the one-frame transforms
+        std::vector<float> w(kUNfft), den(kUHop), t512(2 * kUNfft), t256(2 * kUHalf);
+        const float step = (float)(2.0 * M_PI / (double)kUNfft);                 // torch.hann_window (periodic) in fp32, as make_window() of ade_stft.hip
+        for (int n = 0; n < kUNfft; ++n) w[n] = cosf((float)n * step) * (-0.5f) + 0.5f;
+        for (int n = 0; n < kUHop; ++n) den[n] = (0.0f + w[kUHop + n] * w[kUHop + n]) + w[n] * w[n];      // frame t - 1's second half first, as the one-shot overlap-add sums
+        for (int m = 0; m < kUNfft; ++m) { const double a = 2.0 * M_PI * (double)m / (double)kUNfft; t512[2 * m] = (float)cos(a); t512[2 * m + 1] = (float)-sin(a); }
+        for (int m = 0; m < kUHalf; ++m) { const double a = 2.0 * M_PI * (double)m / (double)kUHalf; t256[2 * m] = (float)cos(a); t256[2 * m + 1] = (float)-sin(a); }
+        fix.push_back({&e->swin, put(w.data(), w.size())});
+        fix.push_back({&e->sden, put(den.data(), den.size())});
+        fix.push_back({&e->stw512, put(t512.data(), t512.size())});
+        fix.push_back({&e->stw256, put(t256.data(), t256.size())});
+        if (!fft::make_plan(kUHalf, &e->p256)) ok = false;
+    }
     // DPGRNN x 2 in GTCRN's lane formats
     for (int i = 0; i < 2 && ok; ++i) {
         const std::string p = "dpgrnn." + std::to_string(i) + ".";
@@ -775,11 +993,12 @@ void UlunasEngine::ctfa(hipStream_t s, const Block& bk, const float* x, const fl
     const long long nfr = (long long)B * T;
     const size_t ta_lds = ta2 ? (size_t)(64 * 3 * 2 * C + 64 * 2 * C + 64 * C + (C >= 32 ? 4 * C * C : 0)) * sizeof(float)
                               : (size_t)(C * 3 * 2 * C + 2 * C * 3 * 2 * C + 2 * C * C + 64 * C) * sizeof(float);
+    float* ta_state = live ? live->ta + live->ta_off[&bk - blocks] : nullptr;      // a push: the recurrence continues from the stream's state
 #define ADE_ULU_TA(CC)                                                                                                                                  \
     if (ta2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ulu_ta2<CC>), dim3((unsigned)B), dim3(256), ta_lds, s, (const float*)zt, bk.ctfa.ta_wih_t, bk.ctfa.ta_whh_t, \
-                                bk.ctfa.ta_bih, bk.ctfa.ta_bhh, bk.ctfa.ta_fc_t, bk.ctfa.ta_fc_b, at, T);                                                \
+                                bk.ctfa.ta_bih, bk.ctfa.ta_bhh, bk.ctfa.ta_fc_t, bk.ctfa.ta_fc_b, at, T, ta_state);                                      \
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ulu_ta<CC>), dim3((unsigned)B), dim3(256), ta_lds, s, (const float*)zt, bk.ctfa.ta_wih_t, bk.ctfa.ta_whh_t, \
-                            bk.ctfa.ta_bih, bk.ctfa.ta_bhh, bk.ctfa.ta_fc_t, bk.ctfa.ta_fc_b, at, T)
+                            bk.ctfa.ta_bih, bk.ctfa.ta_bhh, bk.ctfa.ta_fc_t, bk.ctfa.ta_fc_b, at, T, ta_state)
     switch (C) {               // the channel counts of ULUNAS() (:665); create() rejects anything else
         case 1: ADE_ULU_TA(1); break;
         case 12: ADE_ULU_TA(12); break;
@@ -802,19 +1021,30 @@ float* UlunasEngine::run_block(hipStream_t s, const Block& bk, const float* x, c
         const dim3 grid((unsigned)((long long)B * T));
         const size_t lds = std::max(stage, sq) * sizeof(float);
         float *z = stats ? zt : nullptr, *pq = stats ? pfreq : nullptr;
-#define ADE_ULU_CONV(KT, KF, S, DC) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ulu_conv<KT, KF, S, DC>), grid, dim3(256), lds, s, in, in2, d, o, T, wsize, z, pq)
+        const ClipFrames clip{in, in2};
+        PushFrames push{in, in2, nullptr, nullptr, d.kt - 1};
+        if (live && d.kt > 1) {        // a push: the taps before its first frame come from the stream's history (one convolution per block has kt > 1), which this launch renews
+            const size_t at_ = live->hist_off[&bk - blocks];
+            push.hist_in = live->hist[live->cur] + at_;
+            push.hist_out = live->flushing ? nullptr : live->hist[live->cur ^ 1] + at_;
+        }
+#define ADE_ULU_CONV(KT, KF, S, DC) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ulu_conv<KT, KF, S, DC, ClipFrames>), grid, dim3(256), lds, s, clip, d, o, T, wsize, z, pq)
+#define ADE_ULU_CONV_T(KT, KF, S, DC)                                                                                                                          \
+    if (push.hist_in) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ulu_conv<KT, KF, S, DC, PushFrames>), grid, dim3(256), lds, s, push, d, o, T, wsize, z, pq);       \
+    else ADE_ULU_CONV(KT, KF, S, DC)
         const int key = d.kt * 1000 + d.kf * 100 + d.stride * 10 + d.deconv;       // create() admits exactly these shapes
         switch (key) {
             case 1110: ADE_ULU_CONV(1, 1, 1, false); break;
-            case 3320: ADE_ULU_CONV(3, 3, 2, false); break;
-            case 3321: ADE_ULU_CONV(3, 3, 2, true); break;
-            case 2320: ADE_ULU_CONV(2, 3, 2, false); break;
-            case 2321: ADE_ULU_CONV(2, 3, 2, true); break;
-            case 2310: ADE_ULU_CONV(2, 3, 1, false); break;
-            case 2311: ADE_ULU_CONV(2, 3, 1, true); break;
+            case 3320: ADE_ULU_CONV_T(3, 3, 2, false); break;
+            case 3321: ADE_ULU_CONV_T(3, 3, 2, true); break;
+            case 2320: ADE_ULU_CONV_T(2, 3, 2, false); break;
+            case 2321: ADE_ULU_CONV_T(2, 3, 2, true); break;
+            case 2310: ADE_ULU_CONV_T(2, 3, 1, false); break;
+            case 2311: ADE_ULU_CONV_T(2, 3, 1, true); break;
             case 1510: ADE_ULU_CONV(1, 5, 1, false); break;
             default: ADE_ULU_CONV(1, 5, 1, true); break;     // 1511
         }
+#undef ADE_ULU_CONV_T
 #undef ADE_ULU_CONV
     };
     const int tail_shuffle = (!bk.last && bk.groups == 2) ? 1 : 0;
@@ -889,7 +1119,8 @@ void UlunasEngine::run_net(hipStream_t s, int B) {
         float* o = i == 0 ? dpa : dpb;
         launch_intra_gru(s, View{in, nullptr}, dp[i].intra_gru, rnn, (int)nfr);
         launch_fc_ln_res(s, rnn, View{in, nullptr}, dp[i].fc[0], dp[i].fc_b[0], dp[i].ln_w[0], dp[i].ln_b[0], dpm, B, T);
-        launch_inter_gru(s, dpm, dp[i].inter_gru, rnn, B, T);
+        if (live) hipLaunchKernelGGL(k_ulu_stream_inter_gru, dim3((unsigned)((B * kFw + 15) / 16)), dim3(256), 0, s, (const float*)dpm, dp[i].inter_gru, rnn, B, T, live->inter[i]);
+        else launch_inter_gru(s, dpm, dp[i].inter_gru, rnn, B, T);
         launch_fc_ln_res(s, rnn, View{dpm, nullptr}, dp[i].fc[1], dp[i].fc_b[1], dp[i].ln_w[1], dp[i].ln_b[1], o, B, T);
         in = o;
     }
@@ -903,6 +1134,113 @@ void UlunasEngine::run_net(hipStream_t s, int B) {
     // sigmoid, ERB split, real mask on the spectrum (:649, :734-736, :880); ISTFT; PCM tail (:955, :908)
     hipLaunchKernelGGL(k_ulu_mask, flat(nfr * kUBins), dim3(256), 0, s, dx, erb, (const int*)(d_tab + 2 * kUBands), (const int*)(d_tab + 2 * kUBands + kUHigh), spec, mask_tap, T,
                        nfr * kUBins);
+}
+
+// ---- streams ----------------------------------------------------------------------------------------------------------------------------------------------------
+int UlunasEngine::stream_create(int n_streams, int frames_per_push, void** state, std::string& err) {
+    *state = nullptr;
+    if (frames_per_push == 1)
+        return ufail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: ul_unas: frames_per_push = 1 is not supported: the first push must hold the 257 samples the head reflection reads "
+                                             "(2 <= frames_per_push <= 4096)");
+    if (n_streams < 1 || frames_per_push < 2 || frames_per_push > 4096)
+        return ufail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: ul_unas needs n_streams >= 1 and 2 <= frames_per_push <= 4096");
+    const size_t S = (size_t)n_streams, nfr = S * frames_per_push;
+    if (nfr * 1600 > 0x7fffffffULL) return ufail(err, ADE_ERR_BAD_VALUE, "ade_stream_create: ul_unas: n_streams * frames_per_push exceeds the launch grid");
+    std::unique_ptr<UlunasStream> st(new UlunasStream());
+    st->S = n_streams; st->F = frames_per_push;
+    auto up = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    size_t n_hist = 0, n_ta = 0;
+    for (int i = 0; i < 10; ++i) {
+        st->hist_off[i] = n_hist;
+        st->ta_off[i] = n_ta;
+        const int nc = blocks[i].type == 0 ? 1 : blocks[i].type == 1 ? 2 : 3;
+        for (int c = 0; c < nc; ++c) {
+            const ConvDesc& d = blocks[i].conv[c];
+            if (d.kt > 1) n_hist += (S * (d.kt - 1) * d.Fi * d.Cin + 63) & ~(size_t)63;       // (at most one per block)
+        }
+        n_ta += (S * 2 * blocks[i].cout + 63) & ~(size_t)63;
+    }
+    const size_t b_carry = up(S * kUCarry * sizeof(int16_t)), b_hist = up(n_hist * sizeof(float)), b_half = up(S * kUHop * sizeof(float)), b_ta = up(n_ta * sizeof(float)),
+                 b_inter = up(S * kFw * kCh * sizeof(float));
+    UlunasWork& w = st->work;
+    w.T = frames_per_push;
+    const size_t act = nfr * 1600;             // the carve of reserve(), a push's frames in place of a call's
+    struct Carve { float** p; size_t n; };
+    std::vector<Carve> cs = {{&w.spec, S * 2 * kUBins * frames_per_push}, {&w.bufA, act}, {&w.bufB, act}, {&w.bufC, act}, {&w.bufD, act}, {&w.dpa, nfr * kFw * kCh}, {&w.dpb, nfr * kFw * kCh},
+                             {&w.zt, nfr * 32}, {&w.pfreq, nfr * 132}, {&w.at, nfr * 32}, {&w.fah, nfr * 33 * 8}, {&w.rnn, nfr * kFw * kCh}, {&w.dpm, nfr * kFw * kCh},
+                             {&st->frames, nfr * kUNfft}};
+    for (int i = 0; i < 5; ++i) cs.push_back({&w.skip[i], nfr * (size_t)blocks[i].width * blocks[i].cout});
+    size_t total = 2 * b_carry + 2 * b_hist + 2 * b_half + b_ta + 2 * b_inter;
+    st->reset_bytes = total;
+    for (auto& c : cs) total += up(c.n * sizeof(float));
+    if (hipSetDevice(device) != hipSuccess || hipMalloc(&st->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        return ufail(err, ADE_ERR_DEVICE, "ade_stream_create: hipMalloc of the UL-UNAS stream state failed");
+    }
+    char* p = (char*)st->block;
+    for (int i = 0; i < 2; ++i) { st->carry[i] = (int16_t*)p; p += b_carry; }
+    for (int i = 0; i < 2; ++i) { st->hist[i] = (float*)p; p += b_hist; }
+    for (int i = 0; i < 2; ++i) { st->half[i] = (float*)p; p += b_half; }
+    st->ta = (float*)p; p += b_ta;
+    for (int i = 0; i < 2; ++i) { st->inter[i] = (float*)p; p += b_inter; }
+    for (auto& c : cs) { *c.p = (float*)p; p += up(c.n * sizeof(float)); }
+    *state = st.release();
+    return ADE_OK;
+}
+
+int UlunasEngine::stream_reset(void* state, hipStream_t s, std::string& err) {
+    UlunasStream* st = (UlunasStream*)state;
+    UL_HIP(hipMemsetAsync(st->block, 0, st->reset_bytes, s));
+    st->hops = 0;
+    st->cur = 0;
+    return ADE_OK;
+}
+
+// A push (d_in set: F frames per stream) or the flush (d_in null: frame K, one per stream), everything on `s`.
+int UlunasEngine::stream_step(UlunasStream* st, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) {
+    const bool flush = d_in == nullptr, fresh = st->hops == 0;
+    const int S = st->S, F = flush ? 1 : st->F, N = S * F, nxt = st->cur ^ 1;
+    const float2 *tw512 = reinterpret_cast<const float2*>(stw512), *tw256 = reinterpret_cast<const float2*>(stw256);
+    UlunasWork& w = st->work;
+    // 1. analysis of the frames this step completes, and the next carried input
+    hipLaunchKernelGGL(k_ulu_stream_analysis, dim3((unsigned)(flush ? N : N + S)), dim3(256), 0, s, d_in, (const int16_t*)st->carry[st->cur], st->carry[nxt], F * kUHop, F, N,
+                       flush ? 2 : (fresh ? 1 : 0), p256, tw256, tw512, swin, w.spec);
+    // 2. the network on the stream's buffers with T = F, continued from the stream's state (run_block / ctfa / run_net read `live`)
+    const UlunasWork mine = *this;
+    static_cast<UlunasWork&>(*this) = w;
+    T = F;
+    st->flushing = flush;
+    live = st;
+    run_net(s, S);
+    live = nullptr;
+    static_cast<UlunasWork&>(*this) = mine;
+    // 3. one inverse transform per frame; overlap-add, window-square sum, PCM tail, the next carried half
+    hipLaunchKernelGGL(k_ulu_stream_synthesis, dim3((unsigned)N), dim3(256), 0, s, (const float*)w.spec, F, p256, tw256, tw512, swin, st->frames);
+    const long long total = (long long)N * kUHop, total_all = total + (flush ? 0 : (long long)S * kUHop);
+    hipLaunchKernelGGL(k_ulu_stream_out, dim3((unsigned)((total_all + 255) / 256)), dim3(256), 0, s, (const float*)st->frames, (const float*)st->half[st->cur],
+                       flush ? (float*)nullptr : st->half[nxt], sden, F, fresh ? 1 : 0, d_out, d_f32, total, total_all);
+    UL_HIP(hipGetLastError());
+    if (!flush) { st->cur = nxt; st->hops += st->F; }
+    return ADE_OK;
+}
+
+int UlunasEngine::stream_push(void* state, hipStream_t s, const int16_t* d_in, int16_t* d_out, float* d_f32, std::string& err) {
+    return stream_step((UlunasStream*)state, s, d_in, d_out, d_f32, err);
+}
+
+// The last hop: frame K, whose second half is the reflection of the carried samples, added to the carried half frame.
+int UlunasEngine::stream_flush(void* state, hipStream_t s, int16_t* d_out, float* d_f32, std::string& err) {
+    UlunasStream* st = (UlunasStream*)state;
+    if (st->hops < 2) return ufail(err, ADE_ERR_BAD_VALUE, "ade_stream_flush: ul_unas: nothing pushed since the last reset");
+    return stream_step(st, s, nullptr, d_out, d_f32, err);
+}
+
+void UlunasEngine::stream_destroy(void* state) {
+    UlunasStream* st = (UlunasStream*)state;
+    if (!st) return;
+    (void)hipSetDevice(device);
+    if (st->block) (void)hipFree(st->block);
+    delete st;
 }
 
 int UlunasEngine::tap(hipStream_t s, const char* name, int batch, float* out, size_t count, size_t* written, std::string& err) {

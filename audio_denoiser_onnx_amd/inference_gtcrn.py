@@ -205,7 +205,7 @@ def denoise_streaming(session: InferenceSession, audio: np.ndarray, frames_per_p
     """int16 mono waveform -> int16 denoised waveform of the same length through ONE stateful stream (``--stream N``): no slice edges --
     the result is what the reference's graph would give on the whole file in one call (without its whole-call DC removal), which its
     static export cannot do for files longer than the graph input.  The file is zero-padded to whole pushes; the stream's latency
-    (``delay``: one hop, 256 samples for GTCRN, 960 for DFSMN) is removed again (pushes + flush, the first ``delay`` samples dropped)."""
+    (``delay``: one hop, 256 samples for GTCRN and UL-UNAS, 960 for DFSMN) is removed again (pushes + flush, the first ``delay`` samples dropped)."""
     from .session import StreamingSession
     with StreamingSession(session, 1, frames_per_push) as st:
         P = st.samples_per_push

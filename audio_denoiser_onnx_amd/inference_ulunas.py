@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """The reference's ``UL-UNAS/Inference_UL_UNAS_ONNX.py`` call surface on the MI355X engine.
 
-    python -m audio_denoiser_onnx_amd.inference_ulunas <model_dir_or_.adew> [noisy_16k.wav] [denoised.wav]
+    python -m audio_denoiser_onnx_amd.inference_ulunas <model_dir_or_.adew> [noisy_16k.wav] [denoised.wav] [--sequential | --stream FRAMES]
 
 The reference driver has GTCRN's skeleton (mono int16 at 16 kHz, slices of the static input length at a stride of the output length
 when they differ :328-334, zero-padded tail :145,165, concatenate, trim), so this is ``inference_gtcrn``'s loop on a ``ul_unas`` model:
-all slices of the file go to the GPU as one batch.
+all slices of the file go to the GPU as one batch.  ``--stream FRAMES`` (2 <= FRAMES <= 4096) instead runs the whole file through ONE stateful stream
+(``ade_stream_*`` on the ``ul_unas`` handle) in pushes of FRAMES hops of 256 samples plus the flush: no slice edges, the time-attention and inter-frame GRU states and
+every convolution history carried across the file -- what the reference's graph gives on the whole file in one call.  The file is zero-padded to whole pushes and
+the stream's 256-sample delay is removed again.
 """
 from __future__ import annotations
 

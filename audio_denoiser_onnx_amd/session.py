@@ -372,7 +372,15 @@ class StreamingSession:
     the last 960 input samples, every layer's ``lorder - 1`` frames of memory history and the second half of the last synthesised frame, and pushes plus the flush
     equal the reference's one call on the whole signal, 960 samples later, whatever the push size, bit for bit.  ``flush`` (960 samples) needs at least two hops
     pushed.  Only unfolded int16 handles at 48 kHz in and out stream; the bits of ``process`` on the same signal are not promised (its kernels transform frames in
-    pairs), both are within the family's gates of the oracle."""
+    pairs), both are within the family's gates of the oracle.
+
+    On a UL-UNAS session (16 kHz) a hop is 256 samples and ``delay`` is 256 samples (16 ms), as for GTCRN: frame t is centred on sample 256 t and complete one hop
+    later.  The model is causal from end to end, so the stream carries the last 257 input samples, the last ``kt - 1`` input frames of every (de)convolution with
+    ``kt > 1``, the ten time-attention GRU states, the two inter-frame GRU states and the second half of the last synthesised frame, and pushes plus the flush equal
+    the reference's one call on the whole signal, 256 samples later, whatever the push size, bit for bit.  ``2 <= frames_per_push <= 4096`` (the first push must
+    hold the 257 samples the head reflection reads; 1 raises ValueError).  Only plain int16 handles at 16 kHz in and out stream (static or ``dynamic_axes``
+    manifests; float tensors, other rates and batch-fold raise ``AdeUnsupportedError``); the bits of ``process`` on the same signal are not promised (its STFT
+    transforms frames in pairs), both are within the family's gates of the oracle."""
 
     def __init__(self, session: InferenceSession, n_streams: int, frames_per_push: int):
         self._lib, self._session = session._lib, session
@@ -426,7 +434,7 @@ class StreamingSession:
     def flush(self, want_f32: bool = False):
         """End of the signal: the last hop, int16 (n_streams, 256).  ``concatenate(pushes + [flush])[:, 256:]`` is then exactly the one-shot
         output of the whole signal.  ``reset()`` before pushing again.  In general the flush is ``delay`` samples long (768 for NKF-AEC, 1344 for DFSMN-AEC,
-        960 for DFSMN)."""
+        960 for DFSMN, 256 for UL-UNAS)."""
         out = np.empty((self.n_streams, self.delay), np.int16)
         f32 = np.empty((self.n_streams, self.delay), np.float32) if want_f32 else None
         self._lib.check(self._lib.c.ade_stream_flush(self._h, out.ctypes.data, f32.ctypes.data if want_f32 else None), self._session._h)

@@ -177,8 +177,8 @@ ade_status ade_istft_forward(ade_handle h, const float* d_spec, int batch, int f
  * on the whole signal in one call (every op of the network is causal in time), with two stated differences: the output is one
  * hop (256 samples, 16 ms) behind the input -- a frame is complete one hop after its centre -- with the stream's first hop zero;
  * and the per-call DC removal of GTCRN_CUSTOM.forward (Export_GTCRN.py:647, a mean over the WHOLE call, not computable causally)
- * is not applied.  Plain GTCRN handles (not batch-fold; of the other model families NKF-AEC, DFSMN-AEC and DFSMN stream, see below).  All streams of a handle advance
- * together.  A push is frames_per_push HOPS of ade_stream_hop samples: 256 at 16 kHz for GTCRN, NKF-AEC and DFSMN-AEC, 960 at 48 kHz for DFSMN.  A handle that cannot
+ * is not applied.  Plain GTCRN handles (not batch-fold; of the other model families NKF-AEC, DFSMN-AEC, DFSMN and UL-UNAS stream, see below).  All streams of a handle advance
+ * together.  A push is frames_per_push HOPS of ade_stream_hop samples: 256 at 16 kHz for GTCRN, NKF-AEC, DFSMN-AEC and UL-UNAS, 960 at 48 kHz for DFSMN.  A handle that cannot
  * stream answers ADE_ERR_UNSUPPORTED with a message that names what its family's streams take: int16 PCM in and out at the handle's own model rate (16000 or 48000 Hz).
  * A push of up to 512 frames is ONE kernel launch (the fused chunk kernel continuing from the state its previous launch left); longer pushes, or a
  * stream created while the option "fused" is 0, take the multi-kernel sequence. */
@@ -195,10 +195,10 @@ ade_status ade_stream_push_device(ade_stream_handle s, const int16_t* d_in, int1
 ade_status ade_stream_flush(ade_stream_handle s, int16_t* out_pcm, float* out_f32);
 ade_status ade_stream_reset(ade_stream_handle s);      /* back to a fresh stream (zero state, next push reflects its head) */
 void ade_stream_destroy(ade_stream_handle s);           /* before ade_destroy of its engine */
-/* Samples the stream's output lags its input, which is also the flush length per stream: 256 for a GTCRN stream, 768 for an NKF-AEC stream, 1344 for a DFSMN-AEC stream,
- * 960 for a DFSMN stream. */
+/* Samples the stream's output lags its input, which is also the flush length per stream: 256 for a GTCRN or a UL-UNAS stream, 768 for an NKF-AEC stream, 1344 for a
+ * DFSMN-AEC stream, 960 for a DFSMN stream. */
 ade_status ade_stream_delay(ade_stream_handle s, int* samples);
-/* Samples of one hop, the unit of frames_per_push: 256 for a GTCRN, NKF-AEC or DFSMN-AEC stream (16 kHz), 960 for a DFSMN stream (48 kHz). */
+/* Samples of one hop, the unit of frames_per_push: 256 for a GTCRN, NKF-AEC, DFSMN-AEC or UL-UNAS stream (16 kHz), 960 for a DFSMN stream (48 kHz). */
 ade_status ade_stream_hop(ade_stream_handle s, int* samples);
 
 /* ---- stateful streaming over the NKF-AEC path (model_family "nkf_aec"; the same entry points) -------------------------------
@@ -288,6 +288,42 @@ ade_status ade_stream_hop(ade_stream_handle s, int* samples);
  * its taps in one order from history or push alike, the overlap-add adds at most two frames in ascending order.
  * NOT promised: the bits of ade_process on the same signal.  The one-shot kernels transform frames in pairs, which a stream must not
  * (a frame's rounding would depend on where a push ends); both are held to the same gates against the oracle. */
+
+/* ---- stateful streaming over the UL-UNAS path (model_family "ul_unas", 16 kHz; the same entry points) ----------------------------
+ * ULUNAS_CUSTOM.forward (Export_UL_UNAS.py:848-913) is causal from end to end: every (de)convolution is causal in time (:229-240,
+ * :266-269), the time attention of each cTFA is a forward GRU over frames, its frequency attention and the intra-frame GRU run along
+ * frequency inside one frame, the inter-frame GRU is GTCRN's, and the wrapper removes no DC (REMOVE_DC_OFFSET = False).  So pushes
+ * plus the flush equal the reference's ONE call on the whole signal, one hop (256 samples, 16 ms) later, within the family's gates
+ * (PCM 1 LSB from the exact-table oracle under the host simulator, 2 LSB on the GPU), where the per-slice driver restarts ten
+ * time-attention GRUs, two inter-frame GRUs and every convolution history at each slice.  A stream carries, per independent stream:
+ * the last 257 input samples; the last kt - 1 INPUT frames of every (de)convolution with kt > 1 (for a decoder block the frame of
+ * x + skip, already summed): kt = 3 in the first encoder and the last decoder block, kt = 2 in the two (2, 3) blocks of either side;
+ * the ten time-attention hidden states (2 C floats each); the two inter-frame GRU states (33 x 16 each); the synthesis overlap (the
+ * second half of the last synthesised frame, 256 samples).  The state is one allocation; a reset is one memset.
+ * Eligible handles: plain ul_unas handles with int16 audio at 16 kHz on both sides, from a static or a dynamic_axes manifest (a stream
+ * does not use the window length).  F32 / F16 audio tensors, another input or output rate, or use_batch_fold = 1: ADE_ERR_UNSUPPORTED,
+ * the message names int16 / 16000.  (The engine applies no DC removal for this family, so there is no remove_dc_offset to refuse.)
+ * Buffers: in [n_streams][256 F] int16, F = frames_per_push hops (ade_stream_hop = 256); out the same shape; out_f32 optional float
+ * of the same shape (the waveform before the PCM tail).  2 <= F <= 4096: the first push must hold the 257 samples the head reflection
+ * reads, which is GTCRN's rule; F = 1 answers ADE_ERR_BAD_VALUE with a message that says so.  All streams of a handle advance together.
+ * Output timing: ade_stream_hop and ade_stream_delay are 256.  Frame t is centred on sample 256 t and complete one hop later, as for
+ * GTCRN.  The stream's first 256 output samples are zero; output sample j of the stream is sample j - 256 of the reference's ONE call
+ * on the whole signal of 256 K samples (T = K + 1 frames, 256 K output samples).  A fresh stream's first push of F hops completes the
+ * frames 0 .. F - 1 (the head reflected), every later push F more.
+ * ade_stream_flush returns the last 256 samples per stream (out [n_streams][256]), computed from frame K, whose second half is the
+ * reflection of the last 257 samples -- which is why the input carry reaches back 257 samples and not 256.  After a flush the stream
+ * must be reset before it is pushed again; ade_stream_reset and ade_stream_destroy behave as for the other families.
+ * The push size does not change a bit of the output, PCM and f32, and a stream's bits do not depend on how many other streams share
+ * the handle: every transform holds ONE frame (a 512-point real transform as a 256-point complex FFT plus a split pass, and the
+ * Hermitian inverse of one frame), a convolution sums its taps in one order from history or push alike, the time attention's 64-frame
+ * chunks only decide when a frame's input projections are formed, and the overlap-add adds the two frames of a sample in ascending
+ * order over the one-shot's window-square sum (Hann^2 at half overlap is not constant: a 256-entry table; every sample of the trimmed
+ * one-shot output has both of its frames, so the same table serves the signal's first and last hop).
+ * NOT promised: the bits of ade_process on the same signal.  The one-shot path's generic STFT transforms frames in pairs, paired by
+ * the frame's parity inside the call, which a stream must not (a frame's rounding would depend on where a push ends); both are held
+ * to the same gates against the oracle.
+ * ade_stream_push_device enqueues on the caller's ONE stream and does not synchronise (65 launches per push; the row groups that
+ * ade_process runs on side streams, ADE_ULU_GROUPS, are not used by a stream). */
 
 /* ---- generic STFT_Process operator: any n_fft / win_length / hop / window, for the other model families -------
  * Replaces the reference's STFT_Process module in its 'stft_B' (packed) and 'istft_B' (packed, static_norm=True) forms

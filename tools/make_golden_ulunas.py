@@ -9,6 +9,7 @@ state_dict (convolutions and BatchNorms separate, AffinePReLU affine / slope, th
 own ``prepare_for_export_`` as well as the forward.
 
     python tools/make_golden_ulunas.py     # writes tests/golden/ulunas_seed0.npz
+    python tools/make_golden_ulunas.py --stream     # writes tests/golden/ulunas_seed0_stream.npz (one clip of 20 480 samples, the same network)
 """
 import ast
 import json
@@ -217,6 +218,44 @@ def fold_fixture(seed=0):
                         fold_window_length=np.int64(4096), batch_window_seconds=np.float64(0.256))
     print("fold out", out.shape, int(np.abs(out).max()))
 
+
+def stream_fixture(seed=0, n=20480):
+    """The reference's forward, ONE call, on ONE clip of 20 480 samples (80 hops, 81 frames: past the 64-frame chunk of the time-attention kernel) -- what a stream's
+    pushes plus its flush must reproduce 256 samples later (tests/test_ulunas_stream_gpu.py).  The clip is row 0 of ulunas_seed{seed}.npz (speech) continued by the head
+    of row 1 (noise); the network is that fixture's, so no weights are stored again.  ``wave``: the float waveform before the PCM tail, from an ISTFT without the folded
+    output scale.  tests/golden/ulunas_seed{seed}_stream.npz."""
+    z = np.load(os.path.join(mg.GOLD, f"ulunas_seed{seed}.npz"))
+    pcm = np.ascontiguousarray(np.concatenate((z["pcm_in"][0], z["pcm_in"][1]))[:n])
+    assert pcm.shape == (n,) and pcm.dtype == np.int16
+    ns = import_namespace(n)
+    STFT_Process = import_stft_process("UL-UNAS").STFT_Process
+    out = {}
+    for tag, scale in (("pcm_out", 32767.0), ("wave", 1.0)):
+        stft = STFT_Process(model_type="stft_B", n_fft=ns["NFFT"], hop_len=ns["HOP_LENGTH"], win_length=ns["WINDOW_LENGTH"], max_frames=0,
+                            window_type=ns["WINDOW_TYPE"], center_pad=True, pad_mode=ns["STFT_PAD_MODE"], input_scale=ns["INV_INT16"]).eval()
+        istft = STFT_Process(model_type="istft_B", n_fft=ns["NFFT"], hop_len=ns["HOP_LENGTH"], win_length=ns["WINDOW_LENGTH"],
+                             max_frames=ns["MAX_SIGNAL_LENGTH"], window_type=ns["WINDOW_TYPE"], center_pad=True, pad_mode=ns["STFT_PAD_MODE"],
+                             output_scale=scale, static_norm=True).eval()
+        torch.manual_seed(seed)
+        net = ns["ULUNAS"]().eval()
+        seed_network(net, seed)
+        net.prepare_for_export_()
+        model = ns["ULUNAS_CUSTOM"](net.float(), stft, istft, 16000, 16000, remove_dc_offset=False, use_batch_fold=False, fold_window=0,
+                                    input_scale_folded=True, output_scale_folded=scale != 1.0).eval()
+        if scale == 1.0:
+            ns_f = import_namespace(n, extra={"OUT_AUDIO_DTYPE": "F32"})     # the float output path: no PCM tail (:906-912)
+            model = ns_f["ULUNAS_CUSTOM"](net.float(), stft, istft, 16000, 16000, remove_dc_offset=False, use_batch_fold=False, fold_window=0,
+                                          input_scale_folded=True, output_scale_folded=False).eval()
+        with torch.inference_mode():
+            out[tag] = model(torch.from_numpy(pcm.reshape(1, 1, -1).copy())).numpy().reshape(-1)
+        print(tag, out[tag].shape, out[tag].dtype, float(np.abs(out[tag]).max()))
+    assert out["pcm_out"].dtype == np.int16 and out["wave"].dtype == np.float32 and out["pcm_out"].shape == out["wave"].shape == (n,)
+    np.savez_compressed(os.path.join(mg.GOLD, f"ulunas_seed{seed}_stream.npz"), pcm_in=pcm, pcm_out=out["pcm_out"], wave=out["wave"])
+
+
+if __name__ == "__main__" and "--stream" in sys.argv:
+    stream_fixture()
+    sys.exit(0)
 
 if __name__ == "__main__" and "--float-io" in sys.argv:
     float_io_fixture()
