@@ -149,12 +149,24 @@ __device__ __forceinline__ void front_stage(float* smem, int chunk, const Seg& s
     if (!dc_rows) {
         int s = 0;
         if (((L & 7) == 0) && ((reinterpret_cast<size_t>(row) & 15) == 0)) {      // 8 samples per 16-byte load
+            // Nothing else on the GPU runs while a launch's workgroups sit here, so the row is ONE round trip: all of a lane's loads of 16384 samples (every chunk up
+            // to 1.024 s) are in flight before the first add.  A load past the row's end reads a block of zeros instead -- chosen by address, so that nothing waits on
+            // a loaded value before all are requested (ade_device.h, ld4_or_zero).  An integer sum: the order of the adds does not matter.
+            constexpr int kMeanLoads = 2048 / kFusedThreads;
             const int4* r4 = reinterpret_cast<const int4*>(row);
-#pragma unroll 2
-            for (int i = tid; i < (L >> 3); i += kFusedThreads) {
-                const int4 q = r4[i];
-                s += (int)(short)(q.x & 0xffff) + (q.x >> 16) + (int)(short)(q.y & 0xffff) + (q.y >> 16)
-                   + (int)(short)(q.z & 0xffff) + (q.z >> 16) + (int)(short)(q.w & 0xffff) + (q.w >> 16);
+            const int4* z4 = reinterpret_cast<const int4*>(g_zero4);
+            const int n4 = L >> 3;
+            for (int i0 = tid; i0 < n4; i0 += kMeanLoads * kFusedThreads) {
+                int4 q[kMeanLoads];
+#pragma unroll
+                for (int u = 0; u < kMeanLoads; ++u) {
+                    const int i = i0 + u * kFusedThreads;
+                    q[u] = *(i < n4 ? r4 + i : z4);
+                }
+#pragma unroll
+                for (int u = 0; u < kMeanLoads; ++u)
+                    s += (int)(short)(q[u].x & 0xffff) + (q[u].x >> 16) + (int)(short)(q[u].y & 0xffff) + (q[u].y >> 16)
+                       + (int)(short)(q[u].z & 0xffff) + (q[u].z >> 16) + (int)(short)(q[u].w & 0xffff) + (q[u].w >> 16);
             }
         } else {
             for (int i = tid; i < L; i += kFusedThreads) s += (int)row[i];

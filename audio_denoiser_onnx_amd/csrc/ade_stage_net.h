@@ -578,10 +578,50 @@ template <class G> constexpr size_t dp_smem_bytes() { return (size_t)4 * G::kPma
 // of the same plane and position, which it overwrites.  The LayerNorm of a frame then lives inside ONE 16-lane row: lane j of row t owns columns j
 // and 16 + j of frame t (16 channels each) plus channel j of column 32, so that both statistics are a row-rotation all-reduce in registers -- no LDS round trip and
 // no barrier after the one that follows the Linear (the element-wise part costs per POSITION: it stays one lane per position, not the Linear's tile ownership).  emit_pos(p, y[16]) / emit_one(p, channel, y): the normalised + residual values of an owned position / of the
-// lane's one channel of column 32.  `res`: the residual tensor (quad-planar HBM, plane stride Ps), added here.
+// lane's one channel of column 32.
+//
+// What a lane owns of its LayerNorm row: positions p0 (column j), p1 (column 16 + j) and channel j of p2 (column 32).  Rows beyond the segment recompute its last
+// frame and emit nothing.
+struct LnRow { int p0, p1, p2, j; bool live; };
+__device__ __forceinline__ LnRow ln_row(int tid, int T) {
+    int tq = tid;
+    ADE_OPAQUE_V(tq);                                        // (the row's addresses are its user's own: not shared, and kept live, across the phases of a stage)
+    const int tr = tq >> 4;
+    LnRow r;
+    r.j = tq & 15;
+    r.live = tr < T;
+    const int t = r.live ? tr : T - 1;
+    r.p0 = t * kFw + r.j;
+    r.p1 = r.p0 + 16;
+    r.p2 = t * kFw + 32;
+    return r;
+}
+// The two operands fc_ln_rows needs from outside the LDS planes are fetched by its CALLER, as early as they exist, and handed over in registers:
+//   FcW    the Linear's weights and bias as lane (g, jn) of the matrix tile holds them (8 values);
+//   LnRes  the residual of the lane's LayerNorm row (33 values), out of a quad-planar tensor X of plane stride P: the LDS planes or device memory.
+// Vector memory loads return in order: where both come from device memory, FcW is requested FIRST (the first product waits for it alone) and the residual right
+// behind it -- the Linear pass, its barrier and the statistics then run while the residual is on its way.
+struct FcW { float wa[4]; v4f cb; };
+__device__ __forceinline__ FcW fc_w_ld(const float* __restrict__ fc, const float* __restrict__ fc_b, int tid) {
+    int tq = tid;
+    ADE_OPAQUE_V(tq);
+    const int g = (tq >> 4) & 3, jn = tq & 15;
+    FcW w;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) w.wa[kk] = fc[(4 * g + kk) * 16 + jn];        // A: weight of input channel 4g + kk for output channel jn
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w.cb[r] = fc_b[4 * g + r];
+    return w;
+}
+struct LnRes { float a[16], b[16], e; };
+__device__ __forceinline__ void ln_res_ld(const float* X, int P, const LnRow& r, LnRes& s) {
+    pl_ld16(X, P, r.p0, s.a);
+    pl_ld16(X, P, r.p1, s.b);
+    s.e = X[((size_t)(r.j >> 2) * P + r.p2) * 4 + (r.j & 3)];
+}
 template <class G, class EmitPos, class EmitOne>
-__device__ __forceinline__ void fc_ln_rows(float4* R, const float* __restrict__ fc, const float* __restrict__ fc_b, const float* __restrict__ ln_w,
-                                           const float* __restrict__ ln_b, int T, int P, int tid, const float* __restrict__ res, int Ps, EmitPos emit_pos, EmitOne emit_one) {
+__device__ __forceinline__ void fc_ln_rows(float4* R, const FcW& fw, const float* __restrict__ ln_w, const float* __restrict__ ln_b, int T, int P, int tid,
+                                           const LnRes& rs, EmitPos emit_pos, EmitOne emit_one) {
     constexpr int kFusedThreads = G::kThreads, kPmax = G::kPmax;
     static_assert(kFusedThreads / 16 >= G::kTmax, "one 16-lane row per frame");
     {
@@ -589,12 +629,8 @@ __device__ __forceinline__ void fc_ln_rows(float4* R, const float* __restrict__ 
         int tq = tid;
         ADE_OPAQUE_V(tq);                                    // (this pass's nine tile addresses are its own: not hoisted above the recurrence before the phase)
         const int wave = __builtin_amdgcn_readfirstlane(tq >> 6), g = (tq >> 4) & 3, jn = tq & 15;
-        float wa[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) wa[kk] = fc[(4 * g + kk) * 16 + jn];       // A: weight of input channel 4g + kk for output channel jn
-        v4f cb;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) cb[r] = fc_b[4 * g + r];
+        const float (&wa)[4] = fw.wa;
+        const v4f cb = fw.cb;
 #pragma unroll
         for (int it = 0; it < kTiles; ++it) {
             const int pu = (it * kWaves + wave) * 16 + jn, pos = pu < P ? pu : P - 1;
@@ -608,18 +644,11 @@ __device__ __forceinline__ void fc_ln_rows(float4* R, const float* __restrict__ 
         }
     }
     __syncthreads();
-    int tq = tid;
-    ADE_OPAQUE_V(tq);
-    const int tr = tq >> 4, j = tq & 15;
-    const bool live = tr < T;
-    const int t = live ? tr : T - 1;                         // (rows beyond the segment recompute its last frame and emit nothing)
-    const int p0 = t * kFw + j, p1 = p0 + 16, p2 = t * kFw + 32;
+    const LnRow row = ln_row(tid, T);
+    const int j = row.j, p0 = row.p0, p1 = row.p1, p2 = row.p2;
+    const bool live = row.live;
     float* Rf = reinterpret_cast<float*>(R);
     auto allreduce = [](float s) { s += row_ror<8>(s); s += row_ror<4>(s); s += row_ror<2>(s); s += row_ror<1>(s); return s; };
-    // the residual comes from L2 / HBM (a microsecond or two away with every CU busy): requested HERE, ahead of the statistics, used after them
-    float rs0[16], rs1[16];
-    pl_ld16(res, Ps, p0, rs0);
-    const float re = res[((size_t)(j >> 2) * Ps + p2) * 4 + (j & 3)];
     float v0[16], v1[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -642,20 +671,19 @@ __device__ __forceinline__ void fc_ln_rows(float4* R, const float* __restrict__ 
         ld16(ln_w + j * kCh, gw);
         ld16(ln_b + j * kCh, gb);
 #pragma unroll
-        for (int c = 0; c < 16; ++c) v0[c] = ((v0[c] - mean) * rstd * gw[c] + gb[c]) + rs0[c];
+        for (int c = 0; c < 16; ++c) v0[c] = ((v0[c] - mean) * rstd * gw[c] + gb[c]) + rs.a[c];
         if (live) emit_pos(p0, v0);
     }
     {
         float gw[16], gb[16];
-        pl_ld16(res, Ps, p1, rs1);
         ld16(ln_w + (16 + j) * kCh, gw);
         ld16(ln_b + (16 + j) * kCh, gb);
 #pragma unroll
-        for (int c = 0; c < 16; ++c) v1[c] = ((v1[c] - mean) * rstd * gw[c] + gb[c]) + rs1[c];
+        for (int c = 0; c < 16; ++c) v1[c] = ((v1[c] - mean) * rstd * gw[c] + gb[c]) + rs.b[c];
         if (live) emit_pos(p1, v1);
     }
     {
-        const float ye = (de * rstd * ln_w[32 * kCh + j] + ln_b[32 * kCh + j]) + re;
+        const float ye = (de * rstd * ln_w[32 * kCh + j] + ln_b[32 * kCh + j]) + rs.e;
         if (live) emit_one(p2, j, ye);
     }
 }
@@ -684,14 +712,52 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
     int tid_ = threadIdx.x;
     ADE_OPAQUE_V(tid_);
     const int tid = tid_;
-    for (int i = tid; i < kFw * kCh; i += kFusedThreads) {   // (made visible by the barrier after phase A)
-        lnt[i] = w.intra_ln_w[i];
-        lnt[kFw * kCh + i] = w.intra_ln_b[i];
-    }
+    // A pair of LayerNorm tables on its way into LDS waits in registers: requested with everything else its phase asks device memory for, written once that is
+    // requested too (a copy loop of load -> wait -> LDS write is a chain of dependent round trips, a microsecond or two each with every CU busy).
+    constexpr int kLnPerLane = (kFw * kCh + kFusedThreads - 1) / kFusedThreads;
+    float lnw[kLnPerLane], lnb[kLnPerLane];
+    auto ln_tab_ld = [&](const float* __restrict__ gw, const float* __restrict__ gb) {
+#pragma unroll
+        for (int u = 0; u < kLnPerLane; ++u) {
+            const int i = tid + u * kFusedThreads, ic = i < kFw * kCh ? i : kFw * kCh - 1;
+            lnw[u] = gw[ic];
+            lnb[u] = gb[ic];
+        }
+    };
+    auto ln_tab_st = [&]() {
+#pragma unroll
+        for (int u = 0; u < kLnPerLane; ++u) {
+            const int i = tid + u * kFusedThreads;
+            if (i < kFw * kCh) {
+                lnt[i] = lnw[u];
+                lnt[kFw * kCh + i] = lnb[u];
+            }
+        }
+    };
     const size_t cbase = (size_t)chunk * kCh * Ps + (size_t)sg.t0 * kFw * 4;
     const float* xc = x + cbase;
     float* oc = out + cbase;
 
+    LnRes rx;                                                // phase B's residual: x, taken out of R before phase A's outputs replace it there
+    // Everything phases A and B read from device memory besides x, in ONE round trip: the intra pair of LayerNorm tables, phase B's Linear (a whole recurrence ahead
+    // of its first product) and phase A's GRU weights are all requested before the first of them is used.  (The GRU's rows are loaded whatever the lane's gate and
+    // zeroed by VALUE below: a load under a condition is a branch and a wait of its own.)
+    ln_tab_ld(w.intra_ln_w, w.intra_ln_b);                   // (made visible by the barrier after phase A)
+    const FcW fwB = fc_w_ld(w.intra_fc, w.intra_fc_b, tid);
+    float gw0, gw1, gwh, gb6[6];
+    {
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = (tid >> 4) & 3, j = tid & 15, c = j & 3;
+        const int grp = (wave >> 1) & 1, dir = wave & 1;
+        const float* pk = w.intra_gru + (grp * 8 + dir * 4 + (j >> 2)) * 42;           // [W_ih 3x8 | W_hh 3x4 | b_ih 3 | b_hh 3] of output row (unit j / 4)
+        const int gi = c == 3 ? 2 : c;                                                 // rows r, z, nx read W_i{r, z, n}; row nh reads W_hn
+        gw0 = pk[gi * 8 + g];
+        gw1 = pk[gi * 8 + 4 + g];
+        gwh = pk[24 + (c == 3 ? 0 : c) * 4 + g];
+        const float* pb = w.intra_gru + (grp * 8 + dir * 4 + g) * 42;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) gb6[k] = pb[36 + k];
+    }
+    ln_tab_st();
     ADE_CLK(16);
     // ---- phase A: intra GRNN (GRU(8->4) x 2 groups x 2 directions along F, per frame).                      (:441-446,472-473)
     //      BATCHED over frames on the matrix cores: a wavefront owns one (group, direction) pair for 16 frames, and a step of its 16 recurrences is three
@@ -729,21 +795,16 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
         float ax0, ax1, ah;
         {
             const int c = j & 3;
-            const float* pk = w.intra_gru + (grp * 8 + dir * 4 + (j >> 2)) * 42;       // [W_ih 3x8 | W_hh 3x4 | b_ih 3 | b_hh 3] of output row (unit j / 4)
             const float sc_ = c < 2 ? kS : kN;
-            const int gi = c == 3 ? 2 : c;                                             // rows r, z, nx read W_i{r, z, n}; row nh reads W_hn
-            ax0 = c == 2 ? 0.0f : pk[gi * 8 + g] * sc_;
-            ax1 = c == 2 ? 0.0f : pk[gi * 8 + 4 + g] * sc_;
-            ah = c == 3 ? 0.0f : pk[24 + c * 4 + g] * sc_;
+            ax0 = c == 2 ? 0.0f : gw0 * sc_;
+            ax1 = c == 2 ? 0.0f : gw1 * sc_;
+            ah = c == 3 ? 0.0f : gwh * sc_;
         }
         v4f cb;
-        {
-            const float* pb = w.intra_gru + (grp * 8 + dir * 4 + g) * 42;
-            cb[0] = (pb[36] + pb[39]) * kS;
-            cb[1] = (pb[37] + pb[40]) * kS;
-            cb[2] = pb[41] * kN;
-            cb[3] = pb[38] * kN;
-        }
+        cb[0] = (gb6[0] + gb6[3]) * kS;
+        cb[1] = (gb6[1] + gb6[4]) * kS;
+        cb[2] = gb6[5] * kN;
+        cb[3] = gb6[2] * kN;
         const float* const xr = Rf + ((size_t)(grp * 2) * kPmax + tc * kFw) * 4 + g;      // channel 8 grp + g of the frame's column 0; + 4: the next plane
         float hout[kFw];
         auto run = [&](auto dir_c) {
@@ -768,7 +829,10 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
                 hout[s] = h;
             }
             set_prio(sg.base_prio);
-            __syncthreads();                                 // every wavefront has read its last x column: R takes the rnn outputs
+            // x is the residual of phase B and R still holds all of it (the input of this stage, left there by the stage before or staged above): every lane takes the
+            // 33 values of its LayerNorm row now, and device memory is not asked for them again.  (Here, not at stage entry: 33 fewer registers live across the recurrence.)
+            ln_res_ld(Rf, kPmax, ln_row(tid, T), rx);
+            __syncthreads();                                 // every wavefront has read its last x column and its residual: R takes the rnn outputs
             float* const hw = Rf + ((size_t)(grp * 2 + DIR) * kPmax + tc * kFw) * 4 + g;
             if (live) {
 #pragma unroll
@@ -782,7 +846,9 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
     ADE_CLK(17);
     // ---- phase B: intra Linear + LayerNorm + residual -> mid (registers, and back into R for the inter GRU)
     //      (mid is parked in `out` -- L2-resident, re-read by the same thread in phase D -- instead of 48 live VGPRs)
-    fc_ln_rows<G>(R, w.intra_fc, w.intra_fc_b, lnt, lnt + kFw * kCh, T, P, tid, xc, Ps,
+    //      The inter pair of LayerNorm tables takes the intra pair's place in LDS once this phase is done with it: requested HERE, written after the phase's barrier.
+    ln_tab_ld(w.inter_ln_w, w.inter_ln_b);
+    fc_ln_rows<G>(R, fwB, lnt, lnt + kFw * kCh, T, P, tid, rx,
         [&](int p, const float (&m)[16]) {                  // mid: input of the inter-frame GRU (R) and, parked in the output tensor, the residual of phase D
 #pragma unroll
             for (int q = 0; q < 4; ++q) R[q * kPmax + p] = make_float4(m[4 * q], m[4 * q + 1], m[4 * q + 2], m[4 * q + 3]);
@@ -794,10 +860,7 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
         });
     if (sg.prev && tid == 0) xwait(sg.fi + kXFlagInter + blk, sg.err, xcode(kXFlagInter + blk));    // the previous segment's inter-frame GRU state
     __syncthreads();
-    for (int i = tid; i < kFw * kCh; i += kFusedThreads) {   // phase B is done with the intra pair: the inter pair takes its place (visible after phase C's barrier)
-        lnt[i] = w.inter_ln_w[i];
-        lnt[kFw * kCh + i] = w.inter_ln_b[i];
-    }
+    ln_tab_st();                                             // phase B is done with the intra pair: the inter pair takes its place (visible after phase C's barrier)
     ADE_CLK(18);
 #if ADE_DP_INTER_MFMA
     // ---- phase C: inter GRNN (GRU(8->8) x 2 groups along T, per column), in place in R.                          (:450-455,478-479)
@@ -1007,8 +1070,12 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
     // ---- phase D: inter Linear + LayerNorm + residual(mid) -> out
     {
         const float* nsc = (next_x1 && next_skip) ? next_skip + cbase : nullptr;
-        // (the residual is mid, written by this same lane in phase B: L2-resident)
-        fc_ln_rows<G>(R, w.inter_fc, w.inter_fc_b, lnt, lnt + kFw * kCh, T, P, tid, oc, Ps,
+        // The residual is mid, written by this same lane in phase B: L2-resident, a microsecond or two away with every CU busy -- requested ahead of the Linear pass,
+        // behind its weights (the addresses of an idle row are clamped, not its values: nothing waits on a loaded value before the pass).
+        const FcW fwD = fc_w_ld(w.inter_fc, w.inter_fc_b, tid);
+        LnRes rm;
+        ln_res_ld(oc, Ps, ln_row(tid, T), rm);
+        fc_ln_rows<G>(R, fwD, lnt, lnt + kFw * kCh, T, P, tid, rm,
             [&](int p, const float (&o)[16]) {
                 if (store_lo) {
                     pl_st16(oc, Ps, p, o);
