@@ -181,6 +181,46 @@ __device__ __forceinline__ T cload(const void ADE_CONSTANT_AS* p) {
 typedef const float ADE_CONSTANT_AS* cfptr;
 __device__ __forceinline__ cfptr cptr(const float* p) { return (cfptr)p; }
 
+// PER-LANE accesses to device memory (activations, per-lane weight rows, the exchange area): a pointer that was read out of memory -- a member of ChunkFixed or
+// SegPlan, or of a weight struct fetched with cload<> -- is a GENERIC pointer to the compiler, and every access through it is a FLAT instruction: it counts on the
+// vector-memory counter AND on the LDS counter (so the s_waitcnt lgkmcnt(0) in front of the next ds_read's use also waits for every such load in flight: a prefetch
+// held in registers is drained by the first LDS wait behind it), and it may alias LDS (so it is not moved across LDS writes).  The per-stage kernels do not have the
+// problem: their pointers are kernel arguments, which the compiler knows to be global.  gptr(p) passes p through the GLOBAL address space: the pointer that comes back
+// is the same value in the same (generic) type -- every helper that takes a pointer keeps working on it, and on LDS pointers -- but the compiler's address-space
+// inference now sees where it came from and emits global_load / global_store (vector-memory counter only) for every access derived from it, selects between two such
+// pointers and null included.  Emits no instruction.  Everything these kernels reach through such a pointer is device memory or page-locked host memory (the error
+// word): both are in the global address space; LDS and scratch pointers must NOT be passed through it.  tools/isa_census.py counts what is left (flat_load / flat_store).
+#if defined(__has_attribute)
+#if __has_attribute(address_space)
+#define ADE_GLOBAL_AS __attribute__((address_space(1)))
+#endif
+#endif
+#ifndef ADE_GLOBAL_AS
+#define ADE_GLOBAL_AS
+#endif
+// (The value itself is made opaque on the way, an empty asm on its register: a plain cast there and back is folded away before the inference runs.)
+// gptr: a WAVE-UNIFORM pointer (a base out of a struct plus chunk / segment offsets; it stays in scalar registers -- a per-lane pointer passed here does not
+// compile: "illegal VGPR to SGPR copy"); gptr_lane: a per-lane pointer (the one-word accesses of the exchange primitives below; a 64-bit vector register pair,
+// which is what a FLAT access took as well).
+template <class T> __device__ __forceinline__ T* gptr(T* p) {
+#if defined(__AMDGCN__)
+    T ADE_GLOBAL_AS* q = (T ADE_GLOBAL_AS*)p;
+    asm("" : "+s"(q));
+    return (T*)q;
+#else
+    return p;
+#endif
+}
+template <class T> __device__ __forceinline__ T* gptr_lane(T* p) {
+#if defined(__AMDGCN__)
+    T ADE_GLOBAL_AS* q = (T ADE_GLOBAL_AS*)p;
+    asm("" : "+v"(q));
+    return (T*)q;
+#else
+    return p;
+#endif
+}
+
 // ---- 256-point complex FFT of one wavefront, ONE 256-entry LDS buffer (in place) ---------------------------------
 // Radix-4 Stockham: lane holds z[lane + 64 r] on entry, Z[lane + 64 r] (natural order) on exit.  Every pass reads its
 // four inputs into registers, then (after a barrier) scatters its outputs into the same buffer, so half the LDS of the
@@ -253,10 +293,14 @@ __device__ __forceinline__ void xst4(float* base, int float_off, const float4& v
     u.x = (unsigned)__float_as_int(v.x); u.y = (unsigned)__float_as_int(v.y); u.z = (unsigned)__float_as_int(v.z); u.w = (unsigned)__float_as_int(v.w);
     __builtin_amdgcn_raw_buffer_store_b128(u, r, float_off * 4, 0, 16);
 }
-__device__ __forceinline__ float xld1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void xst1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned xflag_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void xflag_store(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// (the one-word accesses go through gptr_lane(): the exchange area is device memory, and as FLAT accesses the polls and state loads would also sit on the LDS counter)
+__device__ __forceinline__ float xld1(const float* p) { return __hip_atomic_load(gptr_lane(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void xst1(float* p, float v) { __hip_atomic_store(gptr_lane(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned xflag_load(const unsigned* p) { return __hip_atomic_load(gptr_lane(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void xflag_store(unsigned* p, unsigned v) { __hip_atomic_store(gptr_lane(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// the sticky error word (page-locked host memory): system scope, so that every look is a fresh read of the host's copy (a volatile access would stay FLAT)
+__device__ __forceinline__ int xerr_load(const int* p) { return __hip_atomic_load(gptr_lane(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ __forceinline__ void xerr_store(int* p, int v) { __hip_atomic_store(gptr_lane(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 __device__ __forceinline__ void xdrain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 #else
 __device__ __forceinline__ float4 xld4(const float* base, int float_off) { return *reinterpret_cast<const float4*>(base + float_off); }
@@ -265,6 +309,8 @@ __device__ __forceinline__ float xld1(const float* p) { return *p; }
 __device__ __forceinline__ void xst1(float* p, float v) { *p = v; }
 __device__ __forceinline__ unsigned xflag_load(const unsigned* p) { return *(const volatile unsigned*)p; }
 __device__ __forceinline__ void xflag_store(unsigned* p, unsigned v) { *(volatile unsigned*)p = v; }
+__device__ __forceinline__ int xerr_load(const int* p) { return *(const volatile int*)p; }
+__device__ __forceinline__ void xerr_store(int* p, int v) { *(volatile int*)p = v; }
 __device__ __forceinline__ void xdrain() {}
 #endif
 // ONE lane polls ONE flag until it is raised, then lowers it again for the next launch (each flag has exactly one consumer; the kernel
@@ -295,11 +341,10 @@ __device__ __forceinline__ void xwait(unsigned* flag, int* err, int code) {
             const long long dt = wall_clock64() - t0;
             if (dt > (limit >> 4) && !looked) {
                 looked = true;
-                if (*reinterpret_cast<volatile int*>(err) != 0) return;
+                if (xerr_load(err) != 0) return;
             }
             if (dt > limit) {
-                volatile int* const e = reinterpret_cast<volatile int*>(err);
-                if (*e == 0) *e = code;
+                if (xerr_load(err) == 0) xerr_store(err, code);
                 return;
             }
         } while (xflag_load(flag) == 0u);
@@ -309,8 +354,8 @@ __device__ __forceinline__ void xwait(unsigned* flag, int* err, int code) {
 
 // ---- a launch that a host batch streams through (ChunkCall::in_ready / out_done): system-scope words in fine-grained memory, written / polled by the command processor
 #if defined(__AMDGCN__)
-__device__ __forceinline__ unsigned sys_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-__device__ __forceinline__ void sys_store(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ __forceinline__ unsigned sys_load(const unsigned* p) { return __hip_atomic_load(gptr_lane(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ __forceinline__ void sys_store(unsigned* p, unsigned v) { __hip_atomic_store(gptr_lane(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 __device__ __forceinline__ void sys_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, ""); }
 __device__ __forceinline__ void sys_release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, ""); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 #else
@@ -328,8 +373,7 @@ __device__ __forceinline__ void wait_rows_in(const unsigned* ready, unsigned epo
         do {
             __builtin_amdgcn_s_sleep(8);
             if (wall_clock64() - t0 > limit) {
-                volatile int* const e = reinterpret_cast<volatile int*>(err);
-                if (*e == 0) *e = code;
+                if (xerr_load(err) == 0) xerr_store(err, code);
                 break;
             }
         } while (sys_load(ready) != epoch);
@@ -341,7 +385,7 @@ __device__ __forceinline__ void wait_rows_in(const unsigned* ready, unsigned epo
 __device__ __forceinline__ void signal_rows_out(unsigned* count, unsigned* done, unsigned epoch, unsigned wgs) {
     sys_release();
 #if defined(__AMDGCN__)
-    const unsigned old = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned old = __hip_atomic_fetch_add(gptr_lane(count), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #else
     const unsigned old = (*count)++;
 #endif

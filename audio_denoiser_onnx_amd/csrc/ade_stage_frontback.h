@@ -41,18 +41,69 @@ __device__ __forceinline__ float2 rfft_bin(float2 zk, float2 zp, float2 w) {
     return make_float2(e.x + (w.x * o.x - w.y * o.y), e.y + (w.x * o.y + w.y * o.x));
 }
 
-// copy the FFT tables into LDS (L2 is ~1 us away per dependent load); returns LDS-resident views
+// The FFT tables on their way into LDS (L2 is ~1 us away per dependent load), in the form of the DPGRNN's ln_tab_ld / ln_tab_st (ade_stage_net.h): ld() requests
+// everything a lane copies and holds it in registers, st() writes it -- between the two the caller requests whatever else its stage entry reads from device memory,
+// so that the whole entry is ONE round trip.  (A copy loop dst[i] = src[i] is load -> wait -> LDS write per iteration: a chain of dependent round trips.)
+// An index past a table's end is clamped, not branched around: a load under a condition is a wait of its own.  st() returns the LDS-resident views.
 struct LdsTabs { const float* win; const float2* tw256; const float2* tw512; };
+template <int N, int NT> constexpr int per_lane() { return (N + NT - 1) / NT; }
 template <class G>
-__device__ __forceinline__ LdsTabs stage_tables(float* dst, const FftTabs& t, int tid) {
-    constexpr int kFusedThreads = G::kThreads;
-    float* win = dst;
-    float* tw256 = dst + 512;
-    float* tw512 = tw256 + 512;
-    for (int i = tid; i < 512; i += kFusedThreads) { win[i] = t.win[i]; tw256[i] = reinterpret_cast<const float*>(t.tw256)[i]; }
-    for (int i = tid; i < 514; i += kFusedThreads) tw512[i] = reinterpret_cast<const float*>(t.tw512)[i];
-    return LdsTabs{win, reinterpret_cast<const float2*>(tw256), reinterpret_cast<const float2*>(tw512)};
-}
+struct TabRegs {
+    static constexpr int kNT = G::kThreads, kN = per_lane<512, kNT>(), kM = per_lane<514, kNT>();
+    float win[kN], t256[kN], t512[kM];
+    __device__ __forceinline__ void ld(const FftTabs& t, int tid) {
+        const float* const gwin = gptr(t.win);             // (gptr: device memory behind pointers that the single launch reads out of ChunkFixed -- ade_device.h)
+        const float* const g256 = gptr(reinterpret_cast<const float*>(t.tw256));
+        const float* const g512 = gptr(reinterpret_cast<const float*>(t.tw512));
+#pragma unroll
+        for (int u = 0; u < kN; ++u) {
+            const int i = tid + u * kNT, ic = i < 512 ? i : 511;
+            win[u] = gwin[ic];
+            t256[u] = g256[ic];
+        }
+#pragma unroll
+        for (int u = 0; u < kM; ++u) {
+            const int i = tid + u * kNT;
+            t512[u] = g512[i < 514 ? i : 513];
+        }
+    }
+    __device__ __forceinline__ LdsTabs st(float* dst, int tid) const {
+        float* w = dst;
+        float* a = dst + 512;
+        float* b = a + 512;
+#pragma unroll
+        for (int u = 0; u < kN; ++u) {
+            const int i = tid + u * kNT;
+            if (i < 512) { w[i] = win[u]; a[i] = t256[u]; }
+        }
+#pragma unroll
+        for (int u = 0; u < kM; ++u) {
+            const int i = tid + u * kNT;
+            if (i < 514) b[i] = t512[u];
+        }
+        return LdsTabs{w, reinterpret_cast<const float2*>(a), reinterpret_cast<const float2*>(b)};
+    }
+};
+// n <= N values of a device-memory table, lane-strided, on their way into LDS in the same two steps (N: the compile-time capacity; n: what the table holds)
+template <int N, int NT>
+struct CopyRegs {
+    static constexpr int kU = per_lane<N, NT>() > 0 ? per_lane<N, NT>() : 1;
+    float v[kU];
+    __device__ __forceinline__ void ld(const float* src, int n, int tid) {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = tid + u * NT;
+            v[u] = src[i < n ? i : 0];
+        }
+    }
+    __device__ __forceinline__ void st(float* dst, int n, int tid) const {
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int i = tid + u * NT;
+            if (i < n) dst[i] = v[u];
+        }
+    }
+};
 
 // The 4 sample pairs (2n, 2n+1), n = lane + 64 r, of frame t that this lane windows: packed int16 pairs, reflect-padded
 // at the chunk edges (STFT_Process.py:306-309).  Plain loads, no dependence on the DC mean: issued a whole tile ahead.
@@ -125,24 +176,34 @@ __device__ __forceinline__ void front_stage(float* smem, int chunk, const Seg& s
     int tid_ = threadIdx.x;
     ADE_OPAQUE_V(tid_);
     const int tid = tid_, wave = tid >> 6, lane = tid & 63;
-    const int16_t* row = pcm + (size_t)chunk * L;
+    const int16_t* row = gptr(pcm) + (size_t)chunk * L;     // (gptr: see TabRegs)
     const int P0 = T * kF1, P = T * kFw;
-    float* e0c = e0 + (size_t)chunk * kCh * P0;
-    float* e1c = e1 + (size_t)chunk * kCh * P;
-    float* specc = spec + (size_t)chunk * T * 2 * kBinsPad;
+    float* e0c = gptr(e0) + (size_t)chunk * kCh * P0;
+    float* e1c = gptr(e1) + (size_t)chunk * kCh * P;
+    float* specc = gptr(spec) + (size_t)chunk * T * 2 * kBinsPad;
+    const float* const erb_w = gptr(erb.w);
     ADE_CLK(32);
     const bool pair_ok = ((L & 1) == 0) && ((reinterpret_cast<size_t>(row) & 3) == 0);
     int raw[4];                                            // tile 0's samples: in flight while the mean is computed
     const int centre = sg.stream ? 0 : kNfft / 2;
     load_frame_pairs(row, L, tbeg + wave, lane, tbeg + wave < tend, pair_ok, raw, centre);
-    const LdsTabs lt = stage_tables<G>(tabmem, tabs, tid);
+    // Stage entry in ONE round trip: everything a lane copies into LDS (14 values at 256 threads) is requested before the first LDS write -- see TabRegs.
     const bool erb_lds = erb.count <= kBmRows;
-    if (erb_lds)
-        for (int i = tid; i < erb.count * kErbBands; i += kFusedThreads) erbw[i] = erb.w[i];
-    const int erb_s0 = erb.start[lane];
-    for (int i = tid; i < kC0TailW; i += kFusedThreads) w0t[i] = c0.w[i];          // taps k < 3 are the first 27 rows
-    for (int i = tid; i < kC1TailW; i += kFusedThreads) w1t[i] = c1.w[i];          // taps k < 3 are the first 6 (k,g) blocks
-    const float b0t = c0.b[tid & 15], b1t = c1.b[tid & 15];                        // tail biases (lane -> channel, see below)
+    const int erb_n = erb_lds ? erb.count * kErbBands : 0;
+    TabRegs<G> tr;
+    CopyRegs<kBmRows * kErbBands, kFusedThreads> er;
+    CopyRegs<kC0TailW, kFusedThreads> w0r;
+    CopyRegs<kC1TailW, kFusedThreads> w1r;
+    tr.ld(tabs, tid);
+    if (kBmRows > 0) er.ld(erb_w, erb_n, tid);
+    const int erb_s0 = gptr(erb.start)[lane];
+    w0r.ld(gptr(c0.w), kC0TailW, tid);                                             // taps k < 3 are the first 27 rows
+    w1r.ld(gptr(c1.w), kC1TailW, tid);                                             // taps k < 3 are the first 6 (k,g) blocks
+    const float b0t = gptr(c0.b)[tid & 15], b1t = gptr(c1.b)[tid & 15];            // tail biases (lane -> channel, see below)
+    const LdsTabs lt = tr.st(tabmem, tid);
+    if (kBmRows > 0) er.st(erbw, erb_n, tid);
+    w0r.st(w0t, kC0TailW, tid);
+    w1r.st(w1t, kC1TailW, tid);
 
     // ---- F1: DC mean of THIS chunk (exact integer sum, one rounding)                     (Export_GTCRN.py:645-647)
     //      (batch-fold models: the mean is per CALL, over all of its windows, and arrives precomputed in dc_rows)
@@ -178,7 +239,7 @@ __device__ __forceinline__ void front_stage(float* smem, int chunk, const Seg& s
     __syncthreads();
     float dc;
     if (dc_rows) {
-        dc = dc_rows[chunk];
+        dc = gptr(dc_rows)[chunk];
     } else {
         long long tot = 0;
 #pragma unroll
@@ -254,7 +315,7 @@ __device__ __forceinline__ void front_stage(float* smem, int chunk, const Seg& s
                     }
                 }
                 if (erb_lds) erb_merge(erbw, erb.count, erb_s0, buf, lane, fr);
-                else erb_merge(erb.w, erb.count, erb_s0, buf, lane, fr);
+                else erb_merge(erb_w, erb.count, erb_s0, buf, lane, fr);
             }
         }
         __syncthreads();    // feat of the tile complete (and the previous tile's conv1 is done with E0)
@@ -432,21 +493,23 @@ __device__ __forceinline__ void back_stage(float* smem, int chunk, const Seg& sg
     float* w4t = w3t + kC3TailW;                               // [tap 2 | tap 4] x [ci][co]
     // (lean geometry, 40 KB per workgroup: win_sum and the ERB-split start indices are fetched from global memory into registers at the top of each tile / once per
     //  stage, and the parked first hop waits in the spare floats behind this segment's own exchange slot)
-    float* wsum = kLean ? const_cast<float*>(tabs.win_sum) : w4t + kC4TailW;
+    float* wsum = kLean ? const_cast<float*>(gptr(tabs.win_sum)) : w4t + kC4TailW;      // (gptr: see TabRegs)
     int* bss = reinterpret_cast<int*>(wsum + kHop);
-    float* pend = kLean ? sg.xo + kXPendOff : reinterpret_cast<float*>(bss + kErbHigh);  // [256] first hop of a segment that has a predecessor
+    float* pend = kLean ? gptr(sg.xo) + kXPendOff : reinterpret_cast<float*>(bss + kErbHigh);  // [256] first hop of a segment that has a predecessor
     int tid_ = threadIdx.x;
     ADE_OPAQUE_V(tid_);
     const int tid = tid_;
     const int P0 = T * kF1, P = T * kFw;
-    const float* xc = x + (size_t)chunk * kCh * P;
-    const float* e1c = e1 + (size_t)chunk * kCh * P;
-    const float* e0c = e0 + (size_t)chunk * kCh * P0;
-    const float* specc = spec + (size_t)chunk * T * 2 * kBinsPad;
+    const float* xc = gptr(x) + (size_t)chunk * kCh * P;
+    const float* e1c = gptr(e1) + (size_t)chunk * kCh * P;
+    const float* e0c = gptr(e0) + (size_t)chunk * kCh * P0;
+    const float* specc = gptr(spec) + (size_t)chunk * T * 2 * kBinsPad;
+    const float* const bs_w = gptr(bs.w);
+    const int* const bs_start = gptr(bs.start);
     const int trim = sg.stream ? 0 : kHop;                     // one-shot calls drop the first half window of the overlap-add (centre padding); streams emit it, one hop behind
     const int out_len = sg.stream ? kHop * T : kHop * (T - 1);
-    int16_t* po = pcm ? pcm + (size_t)chunk * out_len : nullptr;
-    float* fo32 = f32 ? f32 + (size_t)chunk * out_len : nullptr;
+    int16_t* po = pcm ? gptr(pcm) + (size_t)chunk * out_len : nullptr;
+    float* fo32 = f32 ? gptr(f32) + (size_t)chunk * out_len : nullptr;
     ADE_CLK(48);
 
     // S = (d2 + e1) of a tile: 3 float4 slots per lane on 704 lanes, slot u = plane * 528 + tile position (== the LDS index).
@@ -494,29 +557,42 @@ __device__ __forceinline__ void back_stage(float* smem, int chunk, const Seg& sg
     issue_s(tbeg, true, sa0, sb0);
     float4 ea[2], eb[2];                    // loop-carried: tile k issues tile k+1's (every lane redefines them each time)
     issue_e0(tbeg, true, ea, eb);
-    const LdsTabs lt = stage_tables<G>(tabmem, tabs, tid);
-    if (!kLean)
-        for (int i = tid; i < kHop; i += kFusedThreads) wsum[i] = tabs.win_sum[i];
+    // Stage entry in ONE round trip (see TabRegs): every table value a lane copies into LDS is requested behind the first tile's activations and before the first LDS
+    // write.  (Indices are clamped, values are dropped: no load sits under a condition.)
     const bool bs_lds = bs.count <= kBsCap;
+    const int bs_n = bs_lds ? bs.count * kErbHigh : 0;
+    TabRegs<G> tr;
+    CopyRegs<kHop, kFusedThreads> wsr0;
+    CopyRegs<kBsCap * kErbHigh, kFusedThreads> bsr;
+    tr.ld(tabs, tid);
+    if (!kLean) wsr0.ld(gptr(tabs.win_sum), kHop, tid);
+    bsr.ld(bs_w, bs_n, tid);
     int bs_s[4] = {0, 0, 0, 0};                                // lean: start band of the (at most four) high bins this lane masks: k = lane + 64 r (r = 1 .. 3), k = 256 on lane 0
-    if (bs_lds) {
-        for (int i = tid; i < bs.count * kErbHigh; i += kFusedThreads) bsw[i] = bs.w[i];
-        if (!kLean) {
-            for (int i = tid; i < kErbHigh; i += kFusedThreads) bss[i] = bs.start[i];
-        } else {
-            int tq = tid;
-            ADE_OPAQUE_V(tq);
-            const int lane = tq & 63;
+    int bss_r = 0;                                             // fat: the start index this lane copies into LDS
+    if (!kLean) {
+        static_assert(kLean || kErbHigh <= kFusedThreads, "one ERB-split start index per lane");
+        bss_r = bs_start[tid < kErbHigh ? tid : 0];
+    } else {
+        int tq = tid;
+        ADE_OPAQUE_V(tq);
+        const int lane = tq & 63;
 #pragma unroll
-            for (int r = 1; r < 5; ++r) {
-                const int k = r < 4 ? lane + 64 * r : 256;
-                bs_s[r - 1] = (k >= kErbLow && (r < 4 || lane == 0)) ? bs.start[k - kErbLow] : 0;
-            }
+        for (int r = 1; r < 5; ++r) {
+            const int k = r < 4 ? lane + 64 * r : 256;
+            const int v = bs_start[(k >= kErbLow && (r < 4 || lane == 0)) ? k - kErbLow : 0];
+            bs_s[r - 1] = (bs_lds && k >= kErbLow && (r < 4 || lane == 0)) ? v : 0;
         }
     }
-    for (int i = tid; i < kC3TailW; i += kFusedThreads) w3t[i] = c3.w[(i < 128 ? 2 : 4) * 128 + (i & 127)];
-    for (int i = tid; i < kC4TailW; i += kFusedThreads) w4t[i] = c4.w[(i < 32 ? 2 : 4) * 32 + (i & 31)];
-    const float b3t = c3.b[tid & 15], b4t = c4.b[tid & 1];
+    static_assert(kC3TailW <= kFusedThreads && kC4TailW <= kFusedThreads, "one tail weight of each deconvolution per lane");
+    const float w3r = gptr(c3.w)[((tid & 255) < 128 ? 2 : 4) * 128 + (tid & 127)];
+    const float w4r = gptr(c4.w)[((tid & 63) < 32 ? 2 : 4) * 32 + (tid & 31)];
+    const float b3t = gptr(c3.b)[tid & 15], b4t = gptr(c4.b)[tid & 1];
+    const LdsTabs lt = tr.st(tabmem, tid);
+    if (!kLean) wsr0.st(wsum, kHop, tid);
+    bsr.st(bsw, bs_n, tid);
+    if (!kLean && bs_lds && tid < kErbHigh) bss[tid] = bss_r;
+    if (tid < kC3TailW) w3t[tid] = w3r;
+    if (tid < kC4TailW) w4t[tid] = w4r;
     for (int i = tid; i < kHop; i += kFusedThreads) cbuf[i] = 0.0f;
     const cfptr c3b = cptr(c3.b), c4b = cptr(c4.b), c4w = cptr(c4.w);
     commit_s(sa0, sb0);
@@ -695,9 +771,9 @@ __device__ __forceinline__ void back_stage(float* smem, int chunk, const Seg& sg
                             m1 += mr[kErbPad + kErbLow + jj] * wv;
                         }
                     } else {
-                        const int s0 = bs.start[o];
+                        const int s0 = bs_start[o];
                         for (int n = 0; n < bs.count; ++n) {
-                            const float wv = bs.w[n * kErbHigh + o];
+                            const float wv = bs_w[n * kErbHigh + o];
                             const int jj = min(s0 + n, kErbBands - 1);
                             m0 += mr[kErbLow + jj] * wv;
                             m1 += mr[kErbPad + kErbLow + jj] * wv;

@@ -113,9 +113,11 @@ __device__ __forceinline__ void gtblock_stage(float4* smem, int chunk, const Seg
     ADE_OPAQUE_V(tid_);
     const int tid = tid_;
     const size_t cbase = (size_t)chunk * kCh * Ps + (size_t)sg.t0 * kFw * 4;
-    const float* ac = a + cbase;
-    const float* sc = skip ? skip + cbase : nullptr;
-    float* oc = out + cbase;
+    // (gptr: in the single launch these pointers are read out of ChunkFixed -- see ade_device.h; every per-lane access to device memory below is derived from one)
+    const float* ac = gptr(a) + cbase;
+    const float* sc = skip ? gptr(skip) + cbase : nullptr;
+    float* oc = gptr(out) + cbase;
+    const float* const w_gru = gptr(w.gru);
     const cfptr c_pw1_b = cptr(w.pw1_b), c_dw_b = cptr(w.dw_b), c_pw2_b = cptr(w.pw2_b);
     // Private copies of the weight base pointers: `w` arrives as one 16-dword SGPR tuple, and every use of a member
     // would otherwise restore the whole tuple from its spill lanes (16 v_readlane per weight row).
@@ -352,15 +354,15 @@ __device__ __forceinline__ void gtblock_stage(float4* smem, int chunk, const Seg
     {
         const int j = tid & 15, row = (tid >> 4) & 3;
         const int gsel = (row & 1) ? 2 : (row >> 1);
-        const float* pk = w.gru + j * 78 + 24 + gsel * 16;           // W_h{gate}[j][:]
+        const float* pk = w_gru + j * 78 + 24 + gsel * 16;           // W_h{gate}[j][:]
 #pragma unroll
         for (int m = 0; m < 8; ++m) wr_raw[m] = tid < 64 ? mk2(pk[2 * m], pk[2 * m + 1]) : mk2(0.0f, 0.0f);
-        if (tid < 64) bh_raw = w.gru[j * 78 + 75 + gsel];
+        if (tid < 64) bh_raw = w_gru[j * 78 + 75 + gsel];
     }
     // The next block's skip addend (8 channels per position) is requested HERE, two phases before its use: the compiler
     // drains the vector-memory counter before wave 0 enters the serial recurrence (first use of the weights above), and
     // by then -- after the energy phase -- these HBM loads have landed, so the recurrence does not wait for them.
-    const float* nsc = (next_x1 && next_skip) ? next_skip + cbase : nullptr;
+    const float* nsc = (next_x1 && next_skip) ? gptr(next_skip) + cbase : nullptr;
     float nsk[kPosPerThread][8];
     auto request_next_skip = [&]() {
 #pragma unroll
@@ -400,7 +402,7 @@ __device__ __forceinline__ void gtblock_stage(float4* smem, int chunk, const Seg
                 e[c] += row_ror<1>(e[c]);
                 e[c] = e[c] * (1.0f / (float)kFw);
             }
-            const float* pk = w.gru + j * 78;
+            const float* pk = w_gru + j * 78;
 #pragma unroll
             for (int g = 0; g < 3; ++g) {
                 float sacc = pk[72 + g];
@@ -506,7 +508,7 @@ __device__ __forceinline__ void gtblock_stage(float4* smem, int chunk, const Seg
     // ---- phase 4c: at[t][c] = sigmoid(Linear(16->8)(h_t))                                      (:155)
     for (int idx = tid; idx < T * 8; idx += kFusedThreads) {
         const int t = idx >> 3, c = idx & 7;
-        const float* fr = w.fc + c * 17;
+        const float* fr = gptr(w.fc) + c * 17;
         float s = fr[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) s += fr[k] * HS[t * 16 + k];
@@ -735,25 +737,25 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
         }
     };
     const size_t cbase = (size_t)chunk * kCh * Ps + (size_t)sg.t0 * kFw * 4;
-    const float* xc = x + cbase;
-    float* oc = out + cbase;
+    const float* xc = gptr(x) + cbase;           // (gptr: see gtblock_stage)
+    float* oc = gptr(out) + cbase;
 
     LnRes rx;                                                // phase B's residual: x, taken out of R before phase A's outputs replace it there
     // Everything phases A and B read from device memory besides x, in ONE round trip: the intra pair of LayerNorm tables, phase B's Linear (a whole recurrence ahead
     // of its first product) and phase A's GRU weights are all requested before the first of them is used.  (The GRU's rows are loaded whatever the lane's gate and
     // zeroed by VALUE below: a load under a condition is a branch and a wait of its own.)
-    ln_tab_ld(w.intra_ln_w, w.intra_ln_b);                   // (made visible by the barrier after phase A)
-    const FcW fwB = fc_w_ld(w.intra_fc, w.intra_fc_b, tid);
+    ln_tab_ld(gptr(w.intra_ln_w), gptr(w.intra_ln_b));                   // (made visible by the barrier after phase A)
+    const FcW fwB = fc_w_ld(gptr(w.intra_fc), gptr(w.intra_fc_b), tid);
     float gw0, gw1, gwh, gb6[6];
     {
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = (tid >> 4) & 3, j = tid & 15, c = j & 3;
         const int grp = (wave >> 1) & 1, dir = wave & 1;
-        const float* pk = w.intra_gru + (grp * 8 + dir * 4 + (j >> 2)) * 42;           // [W_ih 3x8 | W_hh 3x4 | b_ih 3 | b_hh 3] of output row (unit j / 4)
+        const float* pk = gptr(w.intra_gru) + (grp * 8 + dir * 4 + (j >> 2)) * 42;           // [W_ih 3x8 | W_hh 3x4 | b_ih 3 | b_hh 3] of output row (unit j / 4)
         const int gi = c == 3 ? 2 : c;                                                 // rows r, z, nx read W_i{r, z, n}; row nh reads W_hn
         gw0 = pk[gi * 8 + g];
         gw1 = pk[gi * 8 + 4 + g];
         gwh = pk[24 + (c == 3 ? 0 : c) * 4 + g];
-        const float* pb = w.intra_gru + (grp * 8 + dir * 4 + g) * 42;
+        const float* pb = gptr(w.intra_gru) + (grp * 8 + dir * 4 + g) * 42;
 #pragma unroll
         for (int k = 0; k < 6; ++k) gb6[k] = pb[36 + k];
     }
@@ -847,7 +849,7 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
     // ---- phase B: intra Linear + LayerNorm + residual -> mid (registers, and back into R for the inter GRU)
     //      (mid is parked in `out` -- L2-resident, re-read by the same thread in phase D -- instead of 48 live VGPRs)
     //      The inter pair of LayerNorm tables takes the intra pair's place in LDS once this phase is done with it: requested HERE, written after the phase's barrier.
-    ln_tab_ld(w.inter_ln_w, w.inter_ln_b);
+    ln_tab_ld(gptr(w.inter_ln_w), gptr(w.inter_ln_b));
     fc_ln_rows<G>(R, fwB, lnt, lnt + kFw * kCh, T, P, tid, rx,
         [&](int p, const float (&m)[16]) {                  // mid: input of the inter-frame GRU (R) and, parked in the output tensor, the residual of phase D
 #pragma unroll
@@ -881,7 +883,7 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
 #pragma unroll
         for (int U = 0; U < 2; ++U) {
             const int c = j & 3;
-            const float* pk = w.inter_gru + (grp * 8 + 4 * U + (j >> 2)) * 54;      // [W_ih 3x8 | W_hh 3x8 | b_ih 3 | b_hh 3] of output row (unit 4 U + j / 4)
+            const float* pk = gptr(w.inter_gru) + (grp * 8 + 4 * U + (j >> 2)) * 54;      // [W_ih 3x8 | W_hh 3x8 | b_ih 3 | b_hh 3] of output row (unit 4 U + j / 4)
             const float sc_ = c < 2 ? kS : kN;
             const int gi = c == 3 ? 2 : c;
 #pragma unroll
@@ -889,7 +891,7 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
                 ax[U][kk] = c == 2 ? 0.0f : pk[gi * 8 + 4 * kk + g] * sc_;
                 ah[U][kk] = c == 3 ? 0.0f : pk[24 + c * 8 + 4 * kk + g] * sc_;
             }
-            const float* pb = w.inter_gru + (grp * 8 + 4 * U + g) * 54;
+            const float* pb = gptr(w.inter_gru) + (grp * 8 + 4 * U + g) * 54;
             cb[U][0] = (pb[48] + pb[51]) * kS;
             cb[U][1] = (pb[49] + pb[52]) * kS;
             cb[U][2] = pb[53] * kN;
@@ -980,7 +982,7 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
         constexpr int kRows = G::kThreads / 16;                      // 16-lane rows of the workgroup
         const int row = tid >> 4, q = tid & 15;
         const int grp = q & 1, unit = q >> 1;
-        const float* pk = w.inter_gru + (grp * 8 + unit) * 54;      // [W_ih 3x8 | W_hh 3x8 | b_ih 3 | b_hh 3] of this output row
+        const float* pk = gptr(w.inter_gru) + (grp * 8 + unit) * 54;      // [W_ih 3x8 | W_hh 3x8 | b_ih 3 | b_hh 3] of this output row
         int ks[8];                                                   // ks[s] = hidden index delivered by rotation s (measured, so the
         ks[0] = unit;                                                // rotation direction convention cannot matter)
 #define ADE_KS(S) ks[S] = ((int)row_ror<2 * S>((float)q)) >> 1;
@@ -1069,10 +1071,10 @@ __device__ __forceinline__ void dpgrnn_stage(float4* smem, int chunk, const Seg&
     ADE_CLK(19);
     // ---- phase D: inter Linear + LayerNorm + residual(mid) -> out
     {
-        const float* nsc = (next_x1 && next_skip) ? next_skip + cbase : nullptr;
+        const float* nsc = (next_x1 && next_skip) ? gptr(next_skip) + cbase : nullptr;
         // The residual is mid, written by this same lane in phase B: L2-resident, a microsecond or two away with every CU busy -- requested ahead of the Linear pass,
         // behind its weights (the addresses of an idle row are clamped, not its values: nothing waits on a loaded value before the pass).
-        const FcW fwD = fc_w_ld(w.inter_fc, w.inter_fc_b, tid);
+        const FcW fwD = fc_w_ld(gptr(w.inter_fc), gptr(w.inter_fc_b), tid);
         LnRes rm;
         ln_res_ld(oc, Ps, ln_row(tid, T), rm);
         fc_ln_rows<G>(R, fwD, lnt, lnt + kFw * kCh, T, P, tid, rm,

@@ -25,8 +25,12 @@ CLASSES = [
     ("mov", r"^v_(mov|accvgpr|swap)"),
     ("convert", r"^v_cvt"),
     ("lds", r"^ds_"),
-    ("vmem_load", r"^(global|buffer|flat|scratch)_load"),
-    ("vmem_store", r"^(global|buffer|flat|scratch)_(store|atomic)"),
+    # FLAT accesses are a class of their own: a flat load counts on the LDS counter as well as on the vector-memory counter, so every LDS wait behind it drains it
+    # (DESIGN.md section 9m).  The GTCRN kernels are meant to have none: a non-zero count here is a pointer that reached a per-lane access without dev::gptr().
+    ("flat_load", r"^flat_load"),
+    ("flat_store", r"^flat_(store|atomic)"),
+    ("vmem_load", r"^(global|buffer|scratch)_load"),
+    ("vmem_store", r"^(global|buffer|scratch)_(store|atomic)"),
     ("smem", r"^s_(load|buffer_load)"),
     ("waitcnt", r"^s_waitcnt"),
     ("barrier", r"^s_barrier"),
@@ -129,10 +133,10 @@ def main():
                 if chain:
                     loops.setdefault(chain, collections.Counter())[classify(o)] += 1
             print(f"region {r:3d}  {len(ops):5d} ops  valu {sum(c[k] for k in VALU):5d}  mfma {c['mfma']:3d}  pkfma {c['fma_packed']:4d}  exp/rcp {c['transcendental']:3d}  lds {c['lds']:3d}  "
-                  f"vmem {c['vmem_load']:3d}/{c['vmem_store']:3d}  rdlane {c['readlane_writelane']:3d}")
+                  f"vmem {c['vmem_load']:3d}/{c['vmem_store']:3d}  flat {c['flat_load']:3d}/{c['flat_store']:3d}  rdlane {c['readlane_writelane']:3d}")
             for chain, lc in loops.items():
                 print(f"            loop {'>'.join(chain):40s} {sum(lc.values()):5d} ops  valu {sum(lc[k] for k in VALU):5d}  pkfma {lc['fma_packed']:4d}  exp/rcp {lc['transcendental']:3d}")
-    print("static total:", sum(total.values()), " VALU (non-MFMA):", sum(total[k] for k in VALU))
+    print("static total:", sum(total.values()), " VALU (non-MFMA):", sum(total[k] for k in VALU), f" FLAT load / store: {total['flat_load']} / {total['flat_store']}")
     for k in names:
         if total[k]:
             print(f"  {k:26s} {total[k]:6d}")
