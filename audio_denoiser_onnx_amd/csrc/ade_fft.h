@@ -17,7 +17,7 @@ namespace fft {
 
 using namespace dev;
 
-constexpr int kMaxPasses = 8;
+constexpr int kMaxPasses = 8;      // reached exactly by five sizes up to 8192 (3^8 = 6561 among them) and exceeded by none: tests/unit/fft_unit.hip `plan` enumerates them
 struct Plan {                      // passed by value to kernels
     int n = 0, passes = 0;
     int radix[kMaxPasses] = {};
@@ -34,7 +34,12 @@ inline bool make_plan(int n, Plan* p) {
     return m == 1 && n >= 2;
 }
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+// The butterflies spell out every fused multiply-add.  Left to -ffp-contract=fast, which product of a sum of two the compiler fuses depends on the code around it: on gfx950
+// forward_static<N> / forward_wave<N> then differed from forward() in the last bits of most words (tests/unit/fft_unit.hip found it; the host simulator never contracts).
+// A product that is the addend of an explicit fmaf has no add to be fused into, and a sum of two fmaf results holds no product.
+// (Which product of cmul is the fused one is free.  The a.x products rounded, the a.y products fused: of the two choices this one keeps UL-UNAS's dynamic-export PCM
+// within tests/test_ulunas_dynamic.py's share of samples one LSB off the reference -- 486 of 9730, the compiler's own mixture gave 485, the other choice 488, the gate is 486.)
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(fmaf(-a.y, b.y, a.x * b.x), fmaf(a.y, b.x, a.x * b.y)); }
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }          // -i a
@@ -49,20 +54,20 @@ __device__ __forceinline__ void dft4(float2* v) {
     v[0] = cadd(a0, a2); v[1] = cadd(a1, a3); v[2] = csub(a0, a2); v[3] = csub(a1, a3);
 }
 __device__ __forceinline__ void dft3(float2* v) {          // w = exp(-2 pi i / 3) = -1/2 - i sqrt(3)/2
+    constexpr float h = 0.86602540378443864676f;
     const float2 s = cadd(v[1], v[2]), d = csub(v[1], v[2]);
-    const float2 m = make_float2(v[0].x - 0.5f * s.x, v[0].y - 0.5f * s.y);
-    const float2 r = make_float2(0.86602540378443864676f * d.y, -0.86602540378443864676f * d.x);      // -i sqrt(3)/2 d
+    const float2 m = make_float2(fmaf(-0.5f, s.x, v[0].x), fmaf(-0.5f, s.y, v[0].y));
     v[0] = cadd(v[0], s);
-    v[1] = cadd(m, r);
-    v[2] = csub(m, r);
+    v[1] = make_float2(fmaf(h, d.y, m.x), fmaf(-h, d.x, m.y));      // m - i sqrt(3)/2 d
+    v[2] = make_float2(fmaf(-h, d.y, m.x), fmaf(h, d.x, m.y));
 }
 __device__ __forceinline__ void dft5(float2* v) {          // exp(-2 pi i k / 5): c1 = cos(72), c2 = cos(144), s1 = sin(72), s2 = sin(144)
     constexpr float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f, s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
     const float2 a1 = cadd(v[1], v[4]), b1 = csub(v[1], v[4]), a2 = cadd(v[2], v[3]), b2 = csub(v[2], v[3]);
-    const float2 m1 = make_float2(v[0].x + c1 * a1.x + c2 * a2.x, v[0].y + c1 * a1.y + c2 * a2.y);
-    const float2 m2 = make_float2(v[0].x + c2 * a1.x + c1 * a2.x, v[0].y + c2 * a1.y + c1 * a2.y);
-    const float2 n1 = mul_mi(make_float2(s1 * b1.x + s2 * b2.x, s1 * b1.y + s2 * b2.y));            // -i (s1 b1 + s2 b2)
-    const float2 n2 = mul_mi(make_float2(s2 * b1.x - s1 * b2.x, s2 * b1.y - s1 * b2.y));            // -i (s2 b1 - s1 b2)
+    const float2 m1 = make_float2(fmaf(c2, a2.x, fmaf(c1, a1.x, v[0].x)), fmaf(c2, a2.y, fmaf(c1, a1.y, v[0].y)));
+    const float2 m2 = make_float2(fmaf(c1, a2.x, fmaf(c2, a1.x, v[0].x)), fmaf(c1, a2.y, fmaf(c2, a1.y, v[0].y)));
+    const float2 n1 = mul_mi(make_float2(fmaf(s2, b2.x, s1 * b1.x), fmaf(s2, b2.y, s1 * b1.y)));          // -i (s1 b1 + s2 b2)
+    const float2 n2 = mul_mi(make_float2(fmaf(-s1, b2.x, s2 * b1.x), fmaf(-s1, b2.y, s2 * b1.y)));        // -i (s2 b1 - s1 b2)
     v[0] = cadd(v[0], cadd(a1, a2));
     v[1] = cadd(m1, n1);
     v[4] = csub(m1, n1);
@@ -128,7 +133,7 @@ __device__ __forceinline__ float2 merge_bin_conj(float2 a, float2 b, float2 t) {
 
 // ---- the same passes with the transform size and its radices known at compile time (the starred models' sizes, and two small ones the host-simulator tests use): trip counts,
 // `j % ns` and the twiddle strides fold into constants, the pass loop unrolls.  The factorisation is make_plan's (4s, then 2s, 3s, 5s), so a size's results are bit-identical
-// to the run-time plan's.
+// to the run-time plan's (tests/unit/fft_unit.hip compares forward_static<N> and forward_wave<N> with forward() word for word, under the host simulator and on gfx950).
 template <int N> struct Static { static constexpr bool known = false; };
 #define ADE_FFT_STATIC(NN, P, R0, R1, R2, R3, R4, R5)                                                                            \
     template <> struct Static<NN> {                                                                                             \
@@ -181,7 +186,7 @@ __device__ __forceinline__ void forward_static(float2* a, float2* b, const float
 
 // ---- the same passes executed by ONE wavefront on a buffer only it touches, IN PLACE: every butterfly of a pass is read into registers before any is written back (LDS
 // serves a wavefront's accesses in program order; wave_sync() keeps the compiler -- and the host simulator's lanes -- to that order), so neither a ping-pong buffer nor a
-// workgroup barrier is needed.  Same butterflies, twiddles and sums as pass_static: bit-identical results.
+// workgroup barrier is needed.  Same butterflies, twiddles and sums as pass_static: bit-identical results (checked by tests/unit/fft_unit.hip).
 template <int R, int N, int NS>
 __device__ __forceinline__ void pass_wave(float2* __restrict__ buf, const float2* __restrict__ tw, int lane) {
     constexpr int nb = N / R, tstep = N / (NS * R), KB = (nb + 63) / 64;
