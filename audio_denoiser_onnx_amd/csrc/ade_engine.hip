@@ -1042,12 +1042,15 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
     const bool fam_dfsmn = e->meta["model_family"] == "dfsmn", fam_melband = e->meta["model_family"] == "mel_band_roformer",
                fam_moss = e->meta["model_family"] == "mossformer2_ss", fam_ulu = e->meta["model_family"] == "ul_unas",
                fam_hg = e->meta["model_family"] == "h_gtcrn", fam_zip = e->meta["model_family"] == "zipenhancer",
-               fam_nkf = e->meta["model_family"] == "nkf_aec", fam_dfa = e->meta["model_family"] == "dfsmn_aec";
+               fam_nkf = e->meta["model_family"] == "nkf_aec", fam_dfa = e->meta["model_family"] == "dfsmn_aec",
+               fam_sda = e->meta["model_family"] == "sdaec";
+    if (fam_sda && !ade::sdaec_create)              // a library linked without csrc/ade_sdaec.hip (weak symbol)
+        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'sdaec' is not built into this library"));
     if (fam_nkf && !ade::nkf_aec_create)            // a library linked without csrc/ade_nkf_aec.hip (weak symbol)
         return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'nkf_aec' is not built into this library"));
     if (fam_dfa && (!ade::dfsmn_aec_create || !ade::nkf_backend_create))     // a library linked without csrc/ade_dfsmn_aec.hip / ade_nkf_aec.hip (weak symbols)
         return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'dfsmn_aec' is not built into this library"));
-    if (fam_dfsmn || fam_melband || fam_moss || fam_ulu || fam_hg || fam_zip || fam_nkf || fam_dfa) {   // DFSMN/Export_DFSMN.py (48 kHz mono) / Mel_Band_Roformer/Stereo/Export_MelBandRoformer.py (44.1 kHz stereo)
+    if (fam_dfsmn || fam_melband || fam_moss || fam_ulu || fam_hg || fam_zip || fam_nkf || fam_dfa || fam_sda) {   // DFSMN/Export_DFSMN.py (48 kHz mono) / Mel_Band_Roformer/Stereo/Export_MelBandRoformer.py (44.1 kHz stereo)
         const std::string fam = e->meta["model_family"];
         const long rate = fam_dfsmn ? 48000 : fam_melband ? 44100 : 16000;
         bool dyn_d = false, fold_d = false;
@@ -1076,6 +1079,16 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
             if (!opt("nfft", "1024") || !opt("hop_length", "256") || !opt("window_length", "1024") || !opt("window_type", "hann") || !opt("pad_mode", "constant") ||
                 !opt("center_pad", "1"))
                 return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: STFT configuration other than 1024/1024/256 hann constant centre-pad"));
+        }
+        if (fam_sda) {      // SDAEC: static axes only (Export_SDAEC.py:47-48 raises), the one STFT and alpha-predictor order the graph is built from (:29-35)
+            if (dyn_d) return bail(fail(e, ADE_ERR_UNSUPPORTED, "sdaec: dynamic_axes=1 does not exist (Export_SDAEC.py:47-48 requires a static audio-length profile)"));
+            auto opt = [&](const char* k, const char* want) { auto it = e->meta.find(k); return it == e->meta.end() || it->second.empty() || it->second == want; };
+            struct { const char *k, *want; } cfg[] = {{"nfft", "319"}, {"window_length", "319"}, {"hop_length", "160"}, {"window_type", "hamming"}, {"center_pad", "1"},
+                                                      {"pad_mode", "constant"}, {"alpha_k", "10"}};
+            for (auto& c : cfg)
+                if (!opt(c.k, c.want))
+                    return bail(fail(e, ADE_ERR_UNSUPPORTED, std::string("sdaec: ") + c.k + " must be " + c.want + " (got '" + e->meta[c.k] +
+                                                             "'): the STFT is 319/319/160 hamming with constant centre pad, alpha_k 10"));
         }
         if (fam_dfa) {      // DFSMN-AEC: the NKF back end and the one set of transforms the graph is built from (Export_DFSMN_AEC.py:39-60, :85-87, :101-110)
             if (dyn_d) return bail(fail(e, ADE_ERR_UNSUPPORTED, "dfsmn_aec: dynamic_axes=1 does not exist with the NKF back end (Export_DFSMN_AEC.py:85-87 forces it off)"));
@@ -1119,13 +1132,17 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         // is GTCRN's sandwich (down-sampling before the * 32767, up-sampling after it, :391-406).
         if (fam_nkf && sri != srm)
             return bail(fail(e, ADE_ERR_UNSUPPORTED, "nkf_aec: in_sample_rate must be the model rate, 16000 Hz (the static export sizes its ISTFT from the input-rate length)"));
-        const bool sand_out = fam_sand || fam_nkf || fam_dfa;          // families whose output edge is the scale-factor sandwich (DFSMN-AEC: Export_DFSMN_AEC.py:1328-1343)
+        // SDAEC's input edge interpolates around the mean removal (Export_SDAEC.py:390-406), which the resampling edge here does not do
+        if (fam_sda && sri != srm)
+            return bail(fail(e, ADE_ERR_UNSUPPORTED, "sdaec: in_sample_rate must be the model rate, 16000 Hz"));
+        if (fam_sda && Ld < 320) return bail(fail(e, ADE_ERR_SHAPE_MISMATCH, "sdaec: input_audio_length must be at least 320 samples"));
+        const bool sand_out = fam_sand || fam_nkf || fam_dfa || fam_sda;          // families whose output edge is the scale-factor sandwich (DFSMN-AEC: Export_DFSMN_AEC.py:1328-1343)
         // Resampling edges exist where the reference's STATIC export is self-consistent: MossFormer2 and DFSMN size their frames from the
         // model-rate length (Export_MossFormer2_SS_16K.py:36-37,99-104; Export_DFSMN.py:48,67).  Mel-Band-Roformer (like GTCRN) and UL-UNAS size
         // the static frame count from the INPUT-rate length (Export_MelBandRoformer.py:52), which only agrees with the STFT at equal rates.
         // H-GTCRN's static export is consistent too (frames from MODEL_AUDIO_LENGTH, Export_H_GTCRN.py:45-46); it interpolates by SCALE FACTOR.
         // ZipEnhancer sizes its frames from MODEL_AUDIO_LENGTH too (Export_ZipEnhancer.py:55, 61) and interpolates by size (:826-832, :905-911).
-        if (rates_differ && !fam_moss && !fam_dfsmn && !fam_hg && !fam_zip && !fam_nkf && !fam_dfa && !(fam_sand && dyn_d))
+        if (rates_differ && !fam_moss && !fam_dfsmn && !fam_hg && !fam_zip && !fam_nkf && !fam_dfa && !fam_sda && !(fam_sand && dyn_d))
             return bail(fail(e, ADE_ERR_UNSUPPORTED, fam + " runs at " + std::to_string(rate) + " Hz in, model and out (its static export has no consistent resampling path" +
                                                      (fam_sand ? ": export with dynamic_axes=1 for other rates)" : ")")));
         if (dyn_d && fold_d) return bail(fail(e, ADE_ERR_BAD_VALUE, "Batch folding requires a static shape (dynamic_axes=0)."));     // (Export_MelBandRoformer.py:46)
@@ -1201,6 +1218,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                        : fam_zip     ? ade::zipenhancer_create(e->tensors, (int)Ld, (int)sub_win, exact_dft, gemm_bf16, dyn_d, device, &e->sub, derr)
                        : fam_nkf     ? ade::nkf_aec_create(e->tensors, (int)Ld, device, &e->sub, derr)
                        : fam_dfa     ? ade::dfsmn_aec_create(e->tensors, (int)Ld, (int)sub_win, exact_dft, device, &e->sub, derr)
+                       : fam_sda     ? ade::sdaec_create(e->tensors, (int)Ld, (int)sub_win, device, &e->sub, derr)
                                      : ade::mossformer_create(e->tensors, (int)Ld, (int)sub_win, dyn_d, device, &e->sub, derr);
         if (rc != ADE_OK) return bail(fail(e, (ade_status)rc, derr));
         e->channels = e->sub->channels();
@@ -1258,7 +1276,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         e->sample_rate = (int)rate;
         e->in_rate = (int)sri;
         e->out_rate = (int)sro;
-        if (fam_dfa) {      // ADE_GRAPH=0: plain launches instead of the captured graph (the option "graph" does the same per handle)
+        if (fam_dfa || fam_sda) {      // ADE_GRAPH=0: plain launches instead of the captured graph (the option "graph" does the same per handle)
             const char* genv = getenv("ADE_GRAPH");
             if (genv && genv[0] == '0') e->use_graph = false;
         }
@@ -1269,7 +1287,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         return ADE_OK;
     }
     if (e->meta["model_family"] != "gtcrn")
-        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family '" + e->meta["model_family"] + "' is not implemented (gtcrn, h_gtcrn, dfsmn, mel_band_roformer, mossformer2_ss, ul_unas, zipenhancer, nkf_aec, dfsmn_aec)"));
+        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family '" + e->meta["model_family"] + "' is not implemented (gtcrn, h_gtcrn, dfsmn, mel_band_roformer, mossformer2_ss, ul_unas, zipenhancer, nkf_aec, dfsmn_aec, sdaec)"));
     bool dyn = false;
     if (!parse_bool(e->meta["dynamic_axes"], &dyn))
         return bail(fail(e, ADE_ERR_BAD_VALUE, "Metadata key dynamic_axes must be a boolean encoded as 1/0, got '" + e->meta["dynamic_axes"] + "'."));

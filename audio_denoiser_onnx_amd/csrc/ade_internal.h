@@ -326,5 +326,7 @@ struct NkfBackend {
 int nkf_backend_create(const std::map<std::string, Tensor>& tensors, int window_len, bool reference_tables, int device, NkfBackend** out, std::string& err) __attribute__((weak));
 // model_family "dfsmn_aec" with light_aec_model NKF (DFSMN_AEC/Export_DFSMN_AEC.py:897-1352), csrc/ade_dfsmn_aec.hip.  Weak, as nkf_aec_create.
 int dfsmn_aec_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, bool exact_dft /* ade_dft_tables = exact: the back end's FFT kernels */, int device, SubEngine** out, std::string& err) __attribute__((weak));
+// model_family "sdaec" (SDAEC/Export_SDAEC.py:54-444: the ICCRN network with its alpha predictor), csrc/ade_sdaec.hip.  Weak, as nkf_aec_create.
+int sdaec_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, int device, SubEngine** out, std::string& err) __attribute__((weak));
 
 }  // namespace ade

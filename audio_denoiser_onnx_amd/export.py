@@ -12,6 +12,7 @@ matrices (``ERB.prepare_for_export_`` :109-114), and write the tensors under the
     python -m audio_denoiser_onnx_amd.export --family ul_unas <model_trained_on_dns3.tar> <out_dir> [--length 16000]
     python -m audio_denoiser_onnx_amd.export --family zipenhancer <pytorch_model.bin> <out_dir> [--length 32000] [--fold]
     python -m audio_denoiser_onnx_amd.export --family nkf_aec <nkf_epoch70.pt> <out_dir> [--length 32000] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
+    python -m audio_denoiser_onnx_amd.export --family sdaec <ICCRN.ckpt> <out_dir> --alpha <alpha.ckpt> [--length 32000] [--fold] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
     python -m audio_denoiser_onnx_amd.export --family dfsmn_aec <dfsmn_state.npz|.pt> <out_dir> --nkf <nkf_epoch70.pt> [--length 32000] [--no-fold] [--vad]
                                                                                        [--in-rate 48000] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
 
@@ -201,6 +202,23 @@ def export_nkf_aec(checkpoint, out_dir, input_audio_length: int = 32000, name: s
     return model_path
 
 
+def export_sdaec(iccrn_ckpt, alpha_ckpt, out_dir, input_audio_length: int = 32000, use_batch_fold: bool = False, name: str = "SDAEC", out_sample_rate: int = 16000,
+                 input_audio_dtype: str = "INT16", output_audio_dtype: str = "INT16") -> Path:
+    """SDAEC's two checkpoints (``ICCRN.ckpt``: the state dict of ``NET``; ``alpha.ckpt``: of ``AlphaPredictor``, Export_SDAEC.py:477, :484) -> ``<name>.adew`` +
+    manifest.  The LayerNorm folds, the two fused Linears, the fused alpha kernel and the cepstral tables are computed here (``sdaec.state_to_blob_tensors``).
+    Static axes and a 16 kHz input only; any output rate; ``use_batch_fold``: windows of 24000 samples."""
+    from . import sdaec
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    model_path = out_dir / f"{name}.adew"
+    net = iccrn_ckpt if isinstance(iccrn_ckpt, Mapping) else load_state_dict(iccrn_ckpt)
+    alpha = alpha_ckpt if isinstance(alpha_ckpt, Mapping) else load_state_dict(alpha_ckpt)
+    save_blob(model_path, sdaec.state_to_blob_tensors(net, alpha))
+    write_metadata(model_path, sdaec.metadata(input_audio_length, use_batch_fold=use_batch_fold, out_sample_rate=out_sample_rate, input_audio_dtype=input_audio_dtype,
+                                              output_audio_dtype=output_audio_dtype, name=name))
+    return model_path
+
+
 def export_dfsmn_aec(dfsmn_checkpoint, nkf_checkpoint, out_dir, input_audio_length: int = 32000, use_batch_fold: bool = True, name: str = "DFSMN_AEC",
                      skip_connect=None, dilation=None, **meta_kw) -> Path:
     """DFSMN-AEC (DFSMN_AEC/Export_DFSMN_AEC.py with the NKF back end) -> ``<name>.adew`` + manifest.  ``dfsmn_checkpoint``: the state dict of the ModelScope
@@ -233,6 +251,11 @@ def main(argv=None) -> int:
         i = argv.index("--nkf")
         nkf_path = argv[i + 1]
         del argv[i:i + 2]
+    alpha_path = None
+    if "--alpha" in argv:
+        i = argv.index("--alpha")
+        alpha_path = argv[i + 1]
+        del argv[i:i + 2]
     for flag in ("--no-fold", "--vad"):
         if flag in argv:
             argv.remove(flag)
@@ -258,7 +281,7 @@ def main(argv=None) -> int:
             i = argv.index(flag)
             gt[key] = conv(argv[i + 1])
             del argv[i:i + 2]
-    if len(argv) != 2 or family not in ("gtcrn", "h_gtcrn", "mel_band_roformer", "mossformer2_ss", "ul_unas", "zipenhancer", "nkf_aec", "dfsmn_aec") or (family == "dfsmn_aec" and not nkf_path):
+    if len(argv) != 2 or family not in ("gtcrn", "h_gtcrn", "mel_band_roformer", "mossformer2_ss", "ul_unas", "zipenhancer", "nkf_aec", "dfsmn_aec", "sdaec") or (family == "dfsmn_aec" and not nkf_path) or (family == "sdaec" and not alpha_path):
         print(__doc__)
         return 2
     model_rate = 44100 if family == "mel_band_roformer" else 16000
@@ -281,6 +304,9 @@ def main(argv=None) -> int:
         path = export_dfsmn_aec(argv[0], nkf_path, argv[1], length or 32000, use_batch_fold=not no_fold, in_sample_rate=gt["in_sample_rate"],
                                 out_sample_rate=gt["out_sample_rate"], input_audio_dtype=gt["input_audio_dtype"], output_audio_dtype=gt["output_audio_dtype"],
                                 output_vad_result=vad)
+    elif family == "sdaec":
+        path = export_sdaec(argv[0], alpha_path, argv[1], length or 32000, use_batch_fold=fold, out_sample_rate=gt["out_sample_rate"],
+                            input_audio_dtype=gt["input_audio_dtype"], output_audio_dtype=gt["output_audio_dtype"])
     elif family == "nkf_aec":
         path = export_nkf_aec(argv[0], argv[1], length or 32000, out_sample_rate=gt["out_sample_rate"], input_audio_dtype=gt["input_audio_dtype"],
                               output_audio_dtype=gt["output_audio_dtype"])

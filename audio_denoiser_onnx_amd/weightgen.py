@@ -97,3 +97,60 @@ def dfsmn_aec_state(seed: int = 0, width: int = 128, hidden: int = 64, depth: in
     net["feature.shift"] = np.full((feat,), -15.0, np.float32)
     net["feature.scale"] = np.full((feat,), 0.2, np.float32)
     return nkf, net, [i % 2 == 0 for i in range(depth)], [dilation] * depth
+
+
+def sdaec_state(seed: int = 0):
+    """Seeded SDAEC weights for benchmarks and smoke runs: ``(iccrn_state, alpha_state)`` under the two checkpoints' key names, the arguments of
+    ``sdaec.state_to_blob_tensors``.  Linear / Conv / LSTM tensors are uniform in +- 1 / sqrt(fan_in) (PyTorch's default range), every LayerNorm has unit
+    weight and a bias of order 1e-4 (the module's own initialisation)."""
+    C, F, FC, K = 20, 160, 81, 10
+    net, alpha = {}, {}
+
+    def put(dst, name, shape, fan_in):
+        dst[name] = tensor(name, shape, 1.0 / np.sqrt(fan_in), seed)
+
+    def lstm(prefix, n_in, hid, layers, bi):
+        for layer in range(layers):
+            for suffix in ("", "_reverse") if bi else ("",):
+                put(net, f"{prefix}.weight_ih_l{layer}{suffix}", (4 * hid, n_in if layer == 0 else hid * (2 if bi else 1)), hid)
+                put(net, f"{prefix}.weight_hh_l{layer}{suffix}", (4 * hid, hid), hid)
+                put(net, f"{prefix}.bias_ih_l{layer}{suffix}", (4 * hid,), hid)
+                put(net, f"{prefix}.bias_hh_l{layer}{suffix}", (4 * hid,), hid)
+
+    def layernorm(prefix, c, f):
+        net[prefix + ".w"] = np.ones((1, c, f, 1), np.float32)
+        net[prefix + ".b"] = np.abs(tensor(prefix + ".b", (1, c, f, 1), 1e-4, seed))
+
+    lstm("in_ch_lstm.lstm2", 4, C, 1, True)
+    put(net, "in_ch_lstm.linear.weight", (C, 2 * C), 2 * C)
+    put(net, "in_ch_lstm.linear.bias", (C,), 2 * C)
+    put(net, "in_conv.weight", (C, C + 4, 1, 1), C + 4)
+    put(net, "in_conv.bias", (C,), C + 4)
+    for n in ("e1", "e2", "e3", "e4", "e5", "d5", "d4", "d3", "d2", "d1"):
+        m, cin = "cfb_" + n, (2 * C if n in ("d4", "d3", "d2", "d1") else C)
+        for conv in ("conv_gate", "conv_input"):
+            put(net, f"{m}.{conv}.weight", (C, cin, 1, 1), cin)
+            put(net, f"{m}.{conv}.bias", (C,), cin)
+        put(net, f"{m}.conv.weight", (C, C, 3, 1), 3 * C)
+        put(net, f"{m}.conv.bias", (C,), 3 * C)
+        layernorm(m + ".LN0", cin, F)
+        layernorm(m + ".LN1", C, F)
+        layernorm(m + ".LN2", C, F)
+        layernorm(m + ".ceps_unit.LN", 2 * C, FC)
+        lstm(m + ".ceps_unit.ch_lstm_f.lstm2", 2 * C, C, 1, True)
+        put(net, m + ".ceps_unit.ch_lstm_f.linear.weight", (2 * C, 2 * C), 2 * C)
+        put(net, m + ".ceps_unit.ch_lstm_f.linear.bias", (2 * C,), 2 * C)
+    layernorm("ln", C, F)
+    lstm("ch_lstm.lstm2", C, 2 * C, 2, False)
+    put(net, "ch_lstm.linear.weight", (C, 2 * C), 2 * C)
+    put(net, "ch_lstm.linear.bias", (C,), 2 * C)
+    lstm("out_ch_lstm.lstm2", 2 * C, C, 1, False)
+    put(net, "out_ch_lstm.linear.weight", (2 * C, C), C)
+    put(net, "out_ch_lstm.linear.bias", (2 * C,), C)
+    put(net, "out_conv.weight", (2, 3 * C, 1, 1), 3 * C)
+    put(net, "out_conv.bias", (2,), 3 * C)
+    put(alpha, "linear1.weight", (1, 2), 2)
+    put(alpha, "linear1.bias", (1,), 2)
+    put(alpha, "linear2.weight", (1, K), K)
+    put(alpha, "linear2.bias", (1,), K)
+    return net, alpha
