@@ -1043,14 +1043,16 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                fam_moss = e->meta["model_family"] == "mossformer2_ss", fam_ulu = e->meta["model_family"] == "ul_unas",
                fam_hg = e->meta["model_family"] == "h_gtcrn", fam_zip = e->meta["model_family"] == "zipenhancer",
                fam_nkf = e->meta["model_family"] == "nkf_aec", fam_dfa = e->meta["model_family"] == "dfsmn_aec",
-               fam_sda = e->meta["model_family"] == "sdaec";
+               fam_sda = e->meta["model_family"] == "sdaec", fam_dec = e->meta["model_family"] == "deep_echo";
     if (fam_sda && !ade::sdaec_create)              // a library linked without csrc/ade_sdaec.hip (weak symbol)
         return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'sdaec' is not built into this library"));
+    if (fam_dec && !ade::deep_echo_create)          // a library linked without csrc/ade_deep_echo.hip (weak symbol)
+        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'deep_echo' is not built into this library"));
     if (fam_nkf && !ade::nkf_aec_create)            // a library linked without csrc/ade_nkf_aec.hip (weak symbol)
         return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'nkf_aec' is not built into this library"));
     if (fam_dfa && (!ade::dfsmn_aec_create || !ade::nkf_backend_create))     // a library linked without csrc/ade_dfsmn_aec.hip / ade_nkf_aec.hip (weak symbols)
         return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family 'dfsmn_aec' is not built into this library"));
-    if (fam_dfsmn || fam_melband || fam_moss || fam_ulu || fam_hg || fam_zip || fam_nkf || fam_dfa || fam_sda) {   // DFSMN/Export_DFSMN.py (48 kHz mono) / Mel_Band_Roformer/Stereo/Export_MelBandRoformer.py (44.1 kHz stereo)
+    if (fam_dfsmn || fam_melband || fam_moss || fam_ulu || fam_hg || fam_zip || fam_nkf || fam_dfa || fam_sda || fam_dec) {   // DFSMN/Export_DFSMN.py (48 kHz mono) / Mel_Band_Roformer/Stereo/Export_MelBandRoformer.py (44.1 kHz stereo)
         const std::string fam = e->meta["model_family"];
         const long rate = fam_dfsmn ? 48000 : fam_melband ? 44100 : 16000;
         bool dyn_d = false, fold_d = false;
@@ -1089,6 +1091,17 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                 if (!opt(c.k, c.want))
                     return bail(fail(e, ADE_ERR_UNSUPPORTED, std::string("sdaec: ") + c.k + " must be " + c.want + " (got '" + e->meta[c.k] +
                                                              "'): the STFT is 319/319/160 hamming with constant centre pad, alpha_k 10"));
+        }
+        if (fam_dec) {      // Deep Echo: the static export only, the one STFT and echo-path order the graph is built from (Export_Deep_Echo.py:33-37)
+            if (dyn_d)
+                return bail(fail(e, ADE_ERR_UNSUPPORTED, "deep_echo: dynamic_axes=1 is not built (the reference has that export, Export_Deep_Echo.py:24; this engine serves the static one)"));
+            auto opt = [&](const char* k, const char* want) { auto it = e->meta.find(k); return it == e->meta.end() || it->second.empty() || it->second == want; };
+            struct { const char *k, *want; } cfg[] = {{"nfft", "319"}, {"window_length", "319"}, {"hop_length", "160"}, {"window_type", "hamming"}, {"center_pad", "1"},
+                                                      {"pad_mode", "constant"}, {"echo_order", "10"}};
+            for (auto& c : cfg)
+                if (!opt(c.k, c.want))
+                    return bail(fail(e, ADE_ERR_UNSUPPORTED, std::string("deep_echo: ") + c.k + " must be " + c.want + " (got '" + e->meta[c.k] +
+                                                             "'): the STFT is 319/319/160 hamming with constant centre pad, echo_order 10"));
         }
         if (fam_dfa) {      // DFSMN-AEC: the NKF back end and the one set of transforms the graph is built from (Export_DFSMN_AEC.py:39-60, :85-87, :101-110)
             if (dyn_d) return bail(fail(e, ADE_ERR_UNSUPPORTED, "dfsmn_aec: dynamic_axes=1 does not exist with the NKF back end (Export_DFSMN_AEC.py:85-87 forces it off)"));
@@ -1136,13 +1149,17 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         if (fam_sda && sri != srm)
             return bail(fail(e, ADE_ERR_UNSUPPORTED, "sdaec: in_sample_rate must be the model rate, 16000 Hz"));
         if (fam_sda && Ld < 320) return bail(fail(e, ADE_ERR_SHAPE_MISMATCH, "sdaec: input_audio_length must be at least 320 samples"));
-        const bool sand_out = fam_sand || fam_nkf || fam_dfa || fam_sda;          // families whose output edge is the scale-factor sandwich (DFSMN-AEC: Export_DFSMN_AEC.py:1328-1343)
+        // Deep Echo's input edge interpolates around the mean removal too (Export_Deep_Echo.py:377-393)
+        if (fam_dec && sri != srm)
+            return bail(fail(e, ADE_ERR_UNSUPPORTED, "deep_echo: in_sample_rate must be the model rate, 16000 Hz"));
+        if (fam_dec && Ld < 320) return bail(fail(e, ADE_ERR_SHAPE_MISMATCH, "deep_echo: input_audio_length must be at least 320 samples"));
+        const bool sand_out = fam_sand || fam_nkf || fam_dfa || fam_sda || fam_dec;          // families whose output edge is the scale-factor sandwich (DFSMN-AEC: Export_DFSMN_AEC.py:1328-1343)
         // Resampling edges exist where the reference's STATIC export is self-consistent: MossFormer2 and DFSMN size their frames from the
         // model-rate length (Export_MossFormer2_SS_16K.py:36-37,99-104; Export_DFSMN.py:48,67).  Mel-Band-Roformer (like GTCRN) and UL-UNAS size
         // the static frame count from the INPUT-rate length (Export_MelBandRoformer.py:52), which only agrees with the STFT at equal rates.
         // H-GTCRN's static export is consistent too (frames from MODEL_AUDIO_LENGTH, Export_H_GTCRN.py:45-46); it interpolates by SCALE FACTOR.
         // ZipEnhancer sizes its frames from MODEL_AUDIO_LENGTH too (Export_ZipEnhancer.py:55, 61) and interpolates by size (:826-832, :905-911).
-        if (rates_differ && !fam_moss && !fam_dfsmn && !fam_hg && !fam_zip && !fam_nkf && !fam_dfa && !fam_sda && !(fam_sand && dyn_d))
+        if (rates_differ && !fam_moss && !fam_dfsmn && !fam_hg && !fam_zip && !fam_nkf && !fam_dfa && !fam_sda && !fam_dec && !(fam_sand && dyn_d))
             return bail(fail(e, ADE_ERR_UNSUPPORTED, fam + " runs at " + std::to_string(rate) + " Hz in, model and out (its static export has no consistent resampling path" +
                                                      (fam_sand ? ": export with dynamic_axes=1 for other rates)" : ")")));
         if (dyn_d && fold_d) return bail(fail(e, ADE_ERR_BAD_VALUE, "Batch folding requires a static shape (dynamic_axes=0)."));     // (Export_MelBandRoformer.py:46)
@@ -1219,6 +1236,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
                        : fam_nkf     ? ade::nkf_aec_create(e->tensors, (int)Ld, device, &e->sub, derr)
                        : fam_dfa     ? ade::dfsmn_aec_create(e->tensors, (int)Ld, (int)sub_win, exact_dft, device, &e->sub, derr)
                        : fam_sda     ? ade::sdaec_create(e->tensors, (int)Ld, (int)sub_win, device, &e->sub, derr)
+                       : fam_dec     ? ade::deep_echo_create(e->tensors, (int)Ld, (int)sub_win, device, &e->sub, derr)
                                      : ade::mossformer_create(e->tensors, (int)Ld, (int)sub_win, dyn_d, device, &e->sub, derr);
         if (rc != ADE_OK) return bail(fail(e, (ade_status)rc, derr));
         e->channels = e->sub->channels();
@@ -1276,7 +1294,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         e->sample_rate = (int)rate;
         e->in_rate = (int)sri;
         e->out_rate = (int)sro;
-        if (fam_dfa || fam_sda) {      // ADE_GRAPH=0: plain launches instead of the captured graph (the option "graph" does the same per handle)
+        if (fam_dfa || fam_sda || fam_dec) {      // ADE_GRAPH=0: plain launches instead of the captured graph (the option "graph" does the same per handle)
             const char* genv = getenv("ADE_GRAPH");
             if (genv && genv[0] == '0') e->use_graph = false;
         }
@@ -1287,7 +1305,7 @@ ade_status ade_create(const char* manifest_json, const void* weights, size_t wei
         return ADE_OK;
     }
     if (e->meta["model_family"] != "gtcrn")
-        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family '" + e->meta["model_family"] + "' is not implemented (gtcrn, h_gtcrn, dfsmn, mel_band_roformer, mossformer2_ss, ul_unas, zipenhancer, nkf_aec, dfsmn_aec, sdaec)"));
+        return bail(fail(e, ADE_ERR_UNSUPPORTED, "model_family '" + e->meta["model_family"] + "' is not implemented (gtcrn, h_gtcrn, dfsmn, mel_band_roformer, mossformer2_ss, ul_unas, zipenhancer, nkf_aec, dfsmn_aec, sdaec, deep_echo)"));
     bool dyn = false;
     if (!parse_bool(e->meta["dynamic_axes"], &dyn))
         return bail(fail(e, ADE_ERR_BAD_VALUE, "Metadata key dynamic_axes must be a boolean encoded as 1/0, got '" + e->meta["dynamic_axes"] + "'."));

@@ -328,5 +328,7 @@ int nkf_backend_create(const std::map<std::string, Tensor>& tensors, int window_
 int dfsmn_aec_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, bool exact_dft /* ade_dft_tables = exact: the back end's FFT kernels */, int device, SubEngine** out, std::string& err) __attribute__((weak));
 // model_family "sdaec" (SDAEC/Export_SDAEC.py:54-444: the ICCRN network with its alpha predictor), csrc/ade_sdaec.hip.  Weak, as nkf_aec_create.
 int sdaec_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, int device, SubEngine** out, std::string& err) __attribute__((weak));
+// model_family "deep_echo" (Deep_Echo_AEC/Export_Deep_Echo.py:79-426: the ICCRN echo-path estimator), csrc/ade_deep_echo.hip.  Weak, as nkf_aec_create.
+int deep_echo_create(const std::map<std::string, Tensor>& tensors, int window_len, int n_win, int device, SubEngine** out, std::string& err) __attribute__((weak));
 
 }  // namespace ade

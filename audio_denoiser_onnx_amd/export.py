@@ -13,6 +13,7 @@ matrices (``ERB.prepare_for_export_`` :109-114), and write the tensors under the
     python -m audio_denoiser_onnx_amd.export --family zipenhancer <pytorch_model.bin> <out_dir> [--length 32000] [--fold]
     python -m audio_denoiser_onnx_amd.export --family nkf_aec <nkf_epoch70.pt> <out_dir> [--length 32000] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
     python -m audio_denoiser_onnx_amd.export --family sdaec <ICCRN.ckpt> <out_dir> --alpha <alpha.ckpt> [--length 32000] [--fold] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
+    python -m audio_denoiser_onnx_amd.export --family deep_echo <model.ckpt> <out_dir> [--length 32000] [--fold] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
     python -m audio_denoiser_onnx_amd.export --family dfsmn_aec <dfsmn_state.npz|.pt> <out_dir> --nkf <nkf_epoch70.pt> [--length 32000] [--no-fold] [--vad]
                                                                                        [--in-rate 48000] [--out-rate 48000] [--in-dtype F32] [--out-dtype F32]
 
@@ -219,6 +220,45 @@ def export_sdaec(iccrn_ckpt, alpha_ckpt, out_dir, input_audio_length: int = 3200
     return model_path
 
 
+def unwrap_deep_echo_checkpoint(checkpoint) -> Dict[str, np.ndarray]:
+    """Export_Deep_Echo.py:56-76: a checkpoint may nest its state dict under ``state_dict`` / ``model_state_dict`` / ``model`` / ``network`` / ``net`` (the first
+    that holds a mapping), and every key may carry a ``module.`` / ``model.`` / ``network.`` / ``net.`` prefix (stripped, in that order, only when ALL keys have it)."""
+    if isinstance(checkpoint, Mapping):
+        for key in ("state_dict", "model_state_dict", "model", "network", "net"):
+            nested = checkpoint.get(key)
+            if isinstance(nested, Mapping):
+                checkpoint = nested
+                break
+    if not isinstance(checkpoint, Mapping):
+        raise TypeError("Unsupported checkpoint format. Expected a state_dict-like mapping.")
+    for prefix in ("module.", "model.", "network.", "net."):
+        if checkpoint and all(k.startswith(prefix) for k in checkpoint):
+            checkpoint = {k[len(prefix):]: v for k, v in checkpoint.items()}
+    return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in checkpoint.items()}
+
+
+def export_deep_echo(checkpoint, out_dir, input_audio_length: int = 32000, use_batch_fold: bool = False, name: str = "Deep_Echo_AEC", out_sample_rate: int = 16000,
+                     input_audio_dtype: str = "INT16", output_audio_dtype: str = "INT16") -> Path:
+    """Deep Echo's ``model.ckpt`` (the state dict of ``NET``, possibly nested and prefixed: ``unwrap_deep_echo_checkpoint``) -> ``<name>.adew`` + manifest.  The
+    LayerNorm folds, the two fused Linears and the cepstral tables are computed here (``deep_echo.state_to_blob_tensors``).  Static axes and a 16 kHz input only;
+    any output rate; ``use_batch_fold``: windows of 24000 samples."""
+    from . import deep_echo
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    model_path = out_dir / f"{name}.adew"
+    if not isinstance(checkpoint, Mapping):
+        path = Path(checkpoint)
+        if path.suffix == ".npz":
+            checkpoint = dict(np.load(path))
+        else:
+            import torch
+            checkpoint = torch.load(str(path), map_location="cpu", weights_only=False)
+    save_blob(model_path, deep_echo.state_to_blob_tensors(unwrap_deep_echo_checkpoint(checkpoint)))
+    write_metadata(model_path, deep_echo.metadata(input_audio_length, use_batch_fold=use_batch_fold, out_sample_rate=out_sample_rate, input_audio_dtype=input_audio_dtype,
+                                                  output_audio_dtype=output_audio_dtype, name=name))
+    return model_path
+
+
 def export_dfsmn_aec(dfsmn_checkpoint, nkf_checkpoint, out_dir, input_audio_length: int = 32000, use_batch_fold: bool = True, name: str = "DFSMN_AEC",
                      skip_connect=None, dilation=None, **meta_kw) -> Path:
     """DFSMN-AEC (DFSMN_AEC/Export_DFSMN_AEC.py with the NKF back end) -> ``<name>.adew`` + manifest.  ``dfsmn_checkpoint``: the state dict of the ModelScope
@@ -281,7 +321,7 @@ def main(argv=None) -> int:
             i = argv.index(flag)
             gt[key] = conv(argv[i + 1])
             del argv[i:i + 2]
-    if len(argv) != 2 or family not in ("gtcrn", "h_gtcrn", "mel_band_roformer", "mossformer2_ss", "ul_unas", "zipenhancer", "nkf_aec", "dfsmn_aec", "sdaec") or (family == "dfsmn_aec" and not nkf_path) or (family == "sdaec" and not alpha_path):
+    if len(argv) != 2 or family not in ("gtcrn", "h_gtcrn", "mel_band_roformer", "mossformer2_ss", "ul_unas", "zipenhancer", "nkf_aec", "dfsmn_aec", "sdaec", "deep_echo") or (family == "dfsmn_aec" and not nkf_path) or (family == "sdaec" and not alpha_path):
         print(__doc__)
         return 2
     model_rate = 44100 if family == "mel_band_roformer" else 16000
@@ -307,6 +347,9 @@ def main(argv=None) -> int:
     elif family == "sdaec":
         path = export_sdaec(argv[0], alpha_path, argv[1], length or 32000, use_batch_fold=fold, out_sample_rate=gt["out_sample_rate"],
                             input_audio_dtype=gt["input_audio_dtype"], output_audio_dtype=gt["output_audio_dtype"])
+    elif family == "deep_echo":
+        path = export_deep_echo(argv[0], argv[1], length or 32000, use_batch_fold=fold, out_sample_rate=gt["out_sample_rate"],
+                                input_audio_dtype=gt["input_audio_dtype"], output_audio_dtype=gt["output_audio_dtype"])
     elif family == "nkf_aec":
         path = export_nkf_aec(argv[0], argv[1], length or 32000, out_sample_rate=gt["out_sample_rate"], input_audio_dtype=gt["input_audio_dtype"],
                               output_audio_dtype=gt["output_audio_dtype"])

@@ -24,7 +24,7 @@ INPUT_NAME = "noisy_audio"       # GTCRN/Export_GTCRN.py:768
 OUTPUT_NAME = "denoised_audio"   # GTCRN/Export_GTCRN.py:769
 AEC_INPUT_NAMES = ("far_end_audio", "near_end_audio")   # NKF_AEC/Export_NKF_AEC.py:524-525
 AEC_OUTPUT_NAME = "aec_audio"
-DFSMN_AEC_INPUT_NAMES = ("near_end_audio", "far_end_audio")   # DFSMN_AEC/Export_DFSMN_AEC.py:1519, SDAEC/Export_SDAEC.py:501: the near end first
+DFSMN_AEC_INPUT_NAMES = ("near_end_audio", "far_end_audio")   # DFSMN_AEC/Export_DFSMN_AEC.py:1519, SDAEC/Export_SDAEC.py:501, Deep_Echo_AEC/Export_Deep_Echo.py:490: the near end first
 VAD_OUTPUT_NAME = "vad_results"
 
 
@@ -95,11 +95,11 @@ class InferenceSession:
         self.out_dtype = {"INT16": np.int16, "F32": np.float32, "F16": np.float16}[reader.string("output_audio_dtype", "INT16")]
         tname = {np.int16: "tensor(int16)", np.float32: "tensor(float)", np.float16: "tensor(float16)"}
         family = reader.string("model_family", "")
-        self._aec = family in ("nkf_aec", "dfsmn_aec", "sdaec")
-        self._aec_near_first = family in ("dfsmn_aec", "sdaec")      # the order of the engine's two planar rows, and of a stream's
+        self._aec = family in ("nkf_aec", "dfsmn_aec", "sdaec", "deep_echo")
+        self._aec_near_first = family in ("dfsmn_aec", "sdaec", "deep_echo")      # the order of the engine's two planar rows, and of a stream's
         # DFSMN-AEC's optional second output: one speech probability per mask frame of every window of the call, float32 (B * windows * frames,) (:1317-1319, :1520)
         self._vad = family == "dfsmn_aec" and bool(reader.optional_bool("output_vad_result", False))
-        if self._aec:      # two graph inputs, one channel each: channels 0 and 1 of the engine's planar rows (Export_NKF_AEC.py:524-525: far end, near end; DFSMN-AEC and SDAEC: near end, far end)
+        if self._aec:      # two graph inputs, one channel each: channels 0 and 1 of the engine's planar rows (Export_NKF_AEC.py:524-525: far end, near end; DFSMN-AEC, SDAEC and Deep Echo: near end, far end)
             self._inputs = [NodeArg(n, [1, 1, io.in_len], tname[self.in_dtype]) for n in (DFSMN_AEC_INPUT_NAMES if self._aec_near_first else AEC_INPUT_NAMES)]
         else:
             self._inputs = [NodeArg(in_name, [1, io.in_channels, io.in_len], tname[self.in_dtype])]
@@ -129,7 +129,7 @@ class InferenceSession:
     def run(self, output_names, input_feed: Dict[str, np.ndarray], return_f32: bool = False):
         """``session.run(None, {"noisy_audio": int16 (B,1,L)})`` -> ``[int16 (B,1,L_out)]`` (+ fp32 pre-PCM tap).
         NKF-AEC: ``{"far_end_audio": (B,1,L), "near_end_audio": (B,1,L)}`` -> ``[aec_audio (B,1,L_out)]``.
-        SDAEC: ``{"near_end_audio": ..., "far_end_audio": ...}`` -> ``[aec_audio]``.
+        SDAEC, Deep Echo: ``{"near_end_audio": ..., "far_end_audio": ...}`` -> ``[aec_audio]``.
         DFSMN-AEC: ``{"near_end_audio": ..., "far_end_audio": ...}`` -> ``[aec_audio]``, and with ``output_vad_result`` a last element ``vad_results`` float32 (B * frames,)."""
         out = self._run_audio(input_feed, return_f32)
         if self._vad:

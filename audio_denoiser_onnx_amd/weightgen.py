@@ -154,3 +154,18 @@ def sdaec_state(seed: int = 0):
     put(alpha, "linear2.weight", (1, K), K)
     put(alpha, "linear2.bias", (1,), K)
     return net, alpha
+
+
+def deep_echo_state(seed: int = 0):
+    """Seeded Deep Echo weights for benchmarks: the state of ``NET`` under the checkpoint's key names, the argument of ``deep_echo.state_to_blob_tensors``.
+    SDAEC's ICCRN state cut down to the two CFBs this network has, with the 20-channel echo-path ``out_conv`` (10 taps x (re, im))."""
+    C, K = 20, 10
+    net, _ = sdaec_state(seed)
+    net = {k: v for k, v in net.items() if not k.startswith("cfb_") or k.startswith(("cfb_e1.", "cfb_d1."))}
+    for conv in ("conv_gate", "conv_input"):
+        net[f"cfb_d1.{conv}.weight"] = tensor(f"deep_echo.cfb_d1.{conv}.weight", (C, C, 1, 1), 1.0 / np.sqrt(C), seed)
+    net["cfb_d1.LN0.w"] = np.ones((1, C, 160, 1), np.float32)
+    net["cfb_d1.LN0.b"] = np.abs(tensor("deep_echo.cfb_d1.LN0.b", (1, C, 160, 1), 1e-4, seed))
+    net["out_conv.weight"] = tensor("deep_echo.out_conv.weight", (2 * K, 3 * C, 1, 1), 1.0 / np.sqrt(3 * C), seed)
+    net["out_conv.bias"] = tensor("deep_echo.out_conv.bias", (2 * K,), 1.0 / np.sqrt(3 * C), seed)
+    return net

@@ -42,7 +42,7 @@ typedef struct ade_engine* ade_handle;
 /* What session.get_inputs()/get_outputs() report for the bound tensors (Inference_GTCRN_ONNX.py:262-267,276-277). */
 typedef struct ade_io_desc {
     int32_t abi_version;
-    int32_t in_channels;       /* 1; 2 for Mel-Band-Roformer stereo (Export_MelBandRoformer.py:714); 2 = (far end, near end) for nkf_aec, (near end, far end) for dfsmn_aec and sdaec */
+    int32_t in_channels;       /* 1; 2 for Mel-Band-Roformer stereo (Export_MelBandRoformer.py:714); 2 = (far end, near end) for nkf_aec, (near end, far end) for dfsmn_aec, sdaec and deep_echo */
     int32_t out_channels;      /* = in_channels, except H-GTCRN: 2 in, 1 out (Export_H_GTCRN.py:1181-1182)             */
     int32_t n_outputs;         /* 1 ("denoised_audio"); 2 for MossFormer2-SS ("separated_0/1", Export_MossFormer2_SS_16K.py:689) */
     int32_t in_len;            /* L: static input length in samples                      */
@@ -69,7 +69,9 @@ typedef struct ade_io_desc {
  * speech probability of output_vad_result is read with ade_debug_tap(h, "vad_results", ...), one float per mask frame of every window of
  * the last call; the optional key ade_dft_tables = "reference" (default) | "exact" selects the back end's transforms) or "sdaec"
  * (SDAEC/Export_SDAEC.py: near-end microphone first, far-end reference second, one channel out; static axes, 16 kHz in, any
- * input_audio_length >= 320, use_batch_fold windows of fold_window_length samples; no streams); the blob then
+ * input_audio_length >= 320, use_batch_fold windows of fold_window_length samples; no streams) or "deep_echo"
+ * (Deep_Echo_AEC/Export_Deep_Echo.py: the same inputs, output and accepted manifests as sdaec, with echo_order = 10 in place of alpha_k;
+ * the reference's dynamic_axes export is not built; no streams); the blob then
  * carries that export's fused buffers. */
 ade_status ade_create(const char* manifest_json, const void* weights, size_t weights_nbytes, int device,
                       ade_handle* out);
